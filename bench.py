@@ -2,6 +2,7 @@
 """Langevin-step throughput of the fused PSGLA+TV HIP step (BASELINE.json configs[1]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 Workload (config.workload): PSGLA, inpainting 50 %, TV denoiser (deepinv TVDenoiser,
@@ -14,8 +15,20 @@ generator, seed_ip = 0, > 0.5).
 Scaling: strong by default -- a batch of 64 chains in total, split
 contiguously over the N ranks (64/N chains per GPU); `--scaling weak` keeps 64 chains per GPU.
 Chains are independent: no collective in the step; chain ids are global, so every chain's
-samples are the same for any N.  One RCCL all_reduce after the timed region combines the
-per-chain MMSE PSNR.
+samples are the same for any N.
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds what
+the headline figure does not need: the MMSE PSNR of the blocks so far (one RCCL all_reduce after
+the timed region combines the per-chain values), `roofline.traffic` from the committed PMC
+profile, and the CPU baseline (the oracle on the host cores, about a minute; `--no-cpu` skips it).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path left for its caller as
+float32 DIR/<name>.npy (DIR/<name>_rank<r>.npy with more than one rank): `x`, the chain state
+after the last timed step (whole while it fits 64 MB), and of the newest stored sample and
+block mean / second moment (`last_sample`, `last_block_mean`, `last_block_sq`) a seeded
+sample of elements each (every run picks the same ones), 64 MB at most in all.  The inputs are
+seeded and the warm-up is undone before the timed steps, so two builds run with the same
+arguments can be compared output for output.
 
 Timed region: exactly K steps (K // G hipGraph replays of G-step graphs + K % G eager launches;
 the device step counter advances the noise counter, block-mean coefficients and sample /
@@ -82,7 +95,11 @@ def parse():
                    help="fused TV kernel (analysis; auto = the library's choice)")
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the batch-1 CPU leg")
     p.add_argument("--cpu-b64-steps", type=int, default=10, help="timed steps of the batch-64 CPU leg (0: skip)")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--full", action="store_true", help="also the MMSE PSNR, roofline.traffic from the committed "
+                   "PMC profile and the CPU baseline (a plain run measures the headline figure only)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the timed path's outputs after the "
+                   "last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     p.add_argument("--pmc-json", default=None, help="PMC summary to report as roofline.traffic (default: the "
                    "committed profile of the dispatched kernel, when it was measured on this workload)")
     return p.parse_args()
@@ -182,6 +199,30 @@ def cpu_baseline(seconds: float, b64_steps: int):
         out["sample"] = (f"batch 64: {n} PSGLA+TV steps (64x3x256x256, one psgla call, after the batch-1 leg) "
                          f"in {dt:.1f} s; " + out["sample"])
     return out
+
+
+DUMP_BUDGET = 64_000_000       # bytes over all dumped arrays
+
+
+def dump_outputs(outdir, arrays, suffix=""):
+    """Write name -> float32 tensor as outdir/<name><suffix>.npy, DUMP_BUDGET bytes at most in all: the first
+    array whole while it fits, of the others (sharing what is left equally) a sorted sample of flattened
+    elements drawn from a fixed seed, the same elements in every run."""
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(0)
+    left = DUMP_BUDGET
+    names = list(arrays)
+    for i, name in enumerate(names):
+        t = arrays[name].detach().to(torch.float32).reshape(-1)
+        keep = min(t.numel(), (left if i == 0 else left // (len(names) - i)) // 4)
+        if keep < t.numel():
+            idx = np.sort(rng.choice(t.numel(), size=keep, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+            a = t.cpu().numpy()
+        else:
+            a = t.cpu().numpy().reshape(arrays[name].shape)
+        left -= a.nbytes
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a)
 
 
 def main():
@@ -299,10 +340,21 @@ def main():
     alg_bytes = algorithmic_bytes_per_launch(B, C, H, W, step0, steps, n_inter, nm)
     achieved = alg_bytes / (live_kern_ms * 1e-3) / 1e9
 
+    if args.dump_outputs:
+        outs = {"x": eng.X}
+        sm, (b1, b2) = eng.samples(), eng.blocks()
+        if sm is not None and len(sm):
+            outs["last_sample"] = sm[-1]
+        if b1 is not None and len(b1):
+            outs["last_block_mean"], outs["last_block_sq"] = b1[-1], b2[-1]
+        dump_outputs(args.dump_outputs, outs, suffix=f"_rank{rank}" if world > 1 else "")
+
     # ---- final reduction (RCCL): per-chain MMSE PSNR of the blocks so far ----
-    from psgla_for_posterior_sampling_amd.sharding import reduce_psnr
-    blocks, _ = eng.blocks()
-    psnr_sum, n_chains = reduce_psnr(blocks, xs, world)
+    psnr_sum, n_chains = None, 0
+    if args.full:
+        from psgla_for_posterior_sampling_amd.sharding import reduce_psnr
+        blocks, _ = eng.blocks()
+        psnr_sum, n_chains = reduce_psnr(blocks, xs, world)
 
     # ---- placement: every rank's device and PCI address, gathered to rank 0 (small metadata) ----
     props = torch.cuda.get_device_properties(dev)
@@ -318,7 +370,7 @@ def main():
     traffic, traffic_info = None, None
     kname = eng.main_kernel            # the kernel the timed graphs launch, once per step
     pmc_json = args.pmc_json or os.path.join(REPO, PMC_PROFILES.get(kname, "none"))
-    if os.path.exists(pmc_json):
+    if args.full and os.path.exists(pmc_json):
         try:
             pj = json.load(open(pmc_json))
             if (pj.get("kernel") == kname and pj.get("workload", {}).get("chains_per_gpu") in (None, B)
@@ -333,7 +385,9 @@ def main():
 
     if rank == 0:
         # the CPU baseline is timed at N = 1 only (rank 0 alone on the host); multi-GPU lines carry null
-        cpu = None if (args.no_cpu or world > 1) else cpu_baseline(args.cpu_seconds, args.cpu_b64_steps)
+        cpu = None
+        if args.full and not args.no_cpu and world == 1:
+            cpu = cpu_baseline(args.cpu_seconds, args.cpu_b64_steps)
         value = total_chains * steps / dt
         roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
@@ -364,7 +418,7 @@ def main():
                        "batch_steps_per_s": round(steps / dt, 2)},
             "roofline": roof,
             "cpu_baseline": cpu,
-            "mmse_psnr_mean_db": round(psnr_sum / max(n_chains, 1), 3),
+            "mmse_psnr_mean_db": None if psnr_sum is None else round(psnr_sum / max(n_chains, 1), 3),
         }
         if world > 1:
             line["config"]["placement"] = placement

@@ -84,7 +84,7 @@ def test_bench_multirank_rehearsal():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = ["bench.py", "--steps", "20", "--warmup", "5", "--no-cpu", "--warmup-seconds", "0"]
+    base = ["bench.py", "--steps", "20", "--warmup", "5", "--full", "--no-cpu", "--warmup-seconds", "0"]
     env = dict(os.environ, PSGLA_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     sock = socket.socket()
     sock.bind(("127.0.0.1", 0))

@@ -25,7 +25,8 @@ python3 -c "
 import json
 for l in open('gpurun_out/${T}_sweep.jsonl'):
     d = json.loads(l); print(d['config']['chains_per_gpu'], d['roofline']['kernel'], d['ms_per_step'], d['roofline']['frac'])"
-timeout -k 10 300 python3 bench.py --pmc-json gpurun_out/prof_${T}64/pmc.json > gpurun_out/${T}_bench.json || exit 1
+PMC=$(find . -maxdepth 3 -path "*/prof_${T}64/pmc.json" -print -quit)    # written by tools/profile_round.sh above
+timeout -k 10 300 python3 bench.py --full --pmc-json "$PMC" > "$(dirname "$(dirname "$PMC")")/${T}_bench.json" || exit 1
 tail -c 900 gpurun_out/${T}_bench.json
 : > gpurun_out/${T}_castle.jsonl
 for args in "10000 1" "10000 1 T" "2000 64" "2000 64 T"; do
