@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define PSGLA_HIP_ABI_VERSION 11
+#define PSGLA_HIP_ABI_VERSION 12
 
 /* Max inner TV iterations the fused (temporally blocked) kernel handles. */
 #define PSGLA_TV_MAX_FUSED_IT 24
@@ -92,6 +92,17 @@ typedef struct PsglaSchedule {
  * barrier (redo[1]), then run their own step.  A run's last step is settled by launch_mask 4 (the pending redo
  * alone, then redo[0] cleared), which the host issues before it reads results.  Without `redo` (or with a larger
  * grid), the finaliser's workgroup recomputes the stopped chains itself, one (plane, segment) / tile after another.
+ *
+ * data_term (ABI 12).  0: the inpainting data term above, computed in the kernel.  1: "Y is given" -- `y` holds this
+ * step's Y = (X + c1*g(X)) + c2*Z, written by an earlier launch on the same stream (deblurring:
+ * psgla_blur_langevin), with row pitch ldw and y_chain_stride == C*H*ldw (0 is accepted only for B == 1);
+ * `mask` may be NULL; c1, c2, sigma2, seed and chain0 are unused; padding columns of Y are never read into the
+ * image.  Everything after Y -- TV iterations, relaxation, state / accumulator / sample stores, early stop, step
+ * advance -- is the same code, on the same kernel psgla_tv_step_kernel names (the tile / stream / band thresholds
+ * were measured for inpainting only).  The parallel redo cannot serve this data term: it would run inside the next
+ * step's launch, after that step's Y has been computed from an X the redo has not yet corrected.  So with
+ * data_term 1 a non-NULL `redo` is rejected, launch_mask 4 is a no-op, and the finaliser's own serial recompute
+ * ("Without `redo`" above) is used; it re-reads the step's Y from the same buffer.  Any other value is rejected.
  * ------------------------------------------------------------------------------- */
 typedef struct PsglaTvStep {
     int32_t B, C, H, W;
@@ -151,6 +162,7 @@ typedef struct PsglaTvStep {
     int32_t* redo;            /* (ABI 11) device int[4 + B], zero-initialised, or NULL: the parallel early-stop
                                  redo (above): [0] pending (bit 0) and the stopped step's TV restart flag
                                  (bit 1), [1] the grid-barrier count, [4 + g] chain g's inner iterations  */
+    int32_t data_term;        /* (ABI 12) 0: inpainting data term in the kernel; 1: y is this step's Y (above) */
 } PsglaTvStep;
 
 int psgla_tv_step(const PsglaTvStep* d, const PsglaSchedule* s, void* stream);
@@ -260,6 +272,18 @@ int psgla_blur_grad(const float* X, const float* y, int64_t y_chain_stride, cons
                     int32_t l, float* g, float* Y, int32_t B, int32_t C, int32_t H, int32_t W, float sigma2,
                     float c1, float c2, uint64_t seed, int32_t chain0, const int64_t* d_step, int64_t step_offset,
                     int32_t exact, void* stream);
+/* (ABI 12) The fused stencil + Langevin update of psgla_blur_grad(..., Y != NULL) for the fused TV step's buffers:
+ *   ld: row pitch (elements) of X, y and Y -- a multiple of 4 >= W, or W; 0 means W.  The circular wrap and the
+ *       noise quads use W: for ld == W the output is bit-identical to psgla_blur_grad's, for ld > W the image columns
+ *       are bit-identical to the contiguous run of the same image (padding columns are neither read nor written);
+ *       y_chain_stride counts elements of the padded layout (C*H*ld per chain, or 0 = shared);
+ *   X_even / X_odd: the kernel reads X_even when the step index *d_step + step_offset is even, X_odd when it is odd,
+ *       so a captured graph of [psgla_blur_langevin, psgla_tv_step(data_term 1)] pairs over the step's ping-pong
+ *       state replays at any step parity with no host input.  The same pointer twice: one input. */
+int psgla_blur_langevin(const float* X_even, const float* X_odd, const float* y, int64_t y_chain_stride,
+                        const float* hconv, const float* hcorr, int32_t l, float* Y, int32_t B, int32_t C, int32_t H,
+                        int32_t W, int32_t ld, float sigma2, float c1, float c2, uint64_t seed, int32_t chain0,
+                        const int64_t* d_step, int64_t step_offset, int32_t exact, void* stream);
 /* Fast mode (exact = 0) runs rank-1 taps (the reference's h^T h kernels) as separable row / column passes
  * (results within fp32 rounding of the 2-D stencil); enable = 0 keeps every call on the 2-D stencil
  * (process-wide switch, for A/B and tests; default 1). */

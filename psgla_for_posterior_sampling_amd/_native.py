@@ -11,7 +11,7 @@ import os
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PSGLA_LIB", os.path.join(_PKG, "libpsgla_hip.so"))
-ABI_VERSION = 11
+ABI_VERSION = 12
 TV_MAX_FUSED_IT = 24
 
 
@@ -46,7 +46,7 @@ class PsglaTvStep(ctypes.Structure):
         ("n_tv", c_i32), ("exact", c_i32), ("seed", c_u64), ("chain0", c_i32), ("advance_step", c_i32),
         ("fresh", c_vp), ("norms", c_vp), ("arrive", c_vp), ("launch_mask", c_i32),
         ("kernel_variant", c_i32), ("stream_wgs", c_i32), ("ldw", c_i32), ("norms_copies", c_i32),
-        ("stream_windows", c_i32), ("redo", c_vp),
+        ("stream_windows", c_i32), ("redo", c_vp), ("data_term", c_i32),
     ]
 
 
@@ -83,6 +83,8 @@ _SIGNATURES = {
                                    c_vp]),
     "psgla_blur_grad": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32,
                                 c_f, c_f, c_f, c_u64, c_i32, c_vp, c_i64, c_i32, c_vp]),
+    "psgla_blur_langevin": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32,
+                                    c_i32, c_f, c_f, c_f, c_u64, c_i32, c_vp, c_i64, c_i32, c_vp]),
     "psgla_blur_set_separable": (c_i32, [c_i32]),
     "psgla_advance_step": (c_i32, [c_vp, c_vp]),
     "psgla_bias_act": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i32, c_vp]),

@@ -28,7 +28,9 @@ from concurrent.futures import ThreadPoolExecutor
 PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
-UNITS = ["api", "tv_stream", "tv_tile", "tv_band", "blur", "elementwise"]
+# (the stream / tile kernels' "Y is given" instances are units of their own -- each includes its kernel's source
+# with another front selected -- so they compile beside the inpainting instances instead of after them)
+UNITS = ["api", "tv_stream", "tv_stream_given", "tv_tile", "tv_tile_given", "tv_band", "blur", "elementwise"]
 SOURCES = [os.path.join(CSRC, u + ".hip") for u in UNITS]
 HEADERS = [os.path.join(CSRC, "noise.hpp"), os.path.join(CSRC, "psgla_common.hpp"),
            os.path.join(REPO, "include", "psgla_hip.h")]
@@ -36,7 +38,8 @@ OUT = os.path.join(PKG, "libpsgla_hip.so")
 OBJ = os.path.join(REPO, "build", "obj")
 ARCH = os.environ.get("PSGLA_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-Wno-inline-asm", "-fPIC"]
-UNIT_FLAGS = {"tv_tile": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
+UNIT_FLAGS = {"tv_tile": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+              "tv_tile_given": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 
 
 def hipcc() -> str:

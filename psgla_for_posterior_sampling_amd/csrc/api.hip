@@ -137,6 +137,7 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
     if (mask == 0) mask = 3;
     // launch_mask 4: settle a pending early-stop redo of the last step (the kernel redoes the stopped chains' part
     // of it, nothing else), then clear the pending flag; only the stream / tile kernels with a redo buffer have one
+    // (with a given Y -- data_term 1 -- there is no parallel redo: launch_mask 4 is a no-op)
     if (mask == 4) {
         if (FRONT != FRONT_INPAINT || !a.redo || (a.tile_r == 0 && !a.stream)) return 0;
         TvArgs s = a;
@@ -146,25 +147,28 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
         if (a.tile_r > 0) {
             const int grid = P * s.nbands * s.st_nsegs;
             const bool gen = !(s.ldw == s.W && s.st_nsegs == 1);
-            s.par_redo = grid_resident(grid, tile_blocks_per_cu(s, EXACT, ALPHA1, gen)) ? 1 : 0;
+            s.par_redo = grid_resident(grid, tile_blocks_per_cu<FRONT_INPAINT>(s, EXACT, ALPHA1, gen)) ? 1 : 0;
             if (!s.par_redo) return 0;   // (the tile kernel's finaliser recomputed stopped chains itself)
-            if (!launch_tile(s, dim3(grid), st, EXACT, ALPHA1, gen))
+            if (!launch_tile<FRONT_INPAINT>(s, dim3(grid), st, EXACT, ALPHA1, gen))
                 return fail(0, "psgla_tv_step: internal error: no tile kernel of this shape");
             rc = launch_check("tv_tile_kernel(redo)");
         } else {
             const int grid = s.split_wgs > 0 ? s.split_wgs : s.st_nvp;
-            s.par_redo = grid_resident(grid, stream_blocks_per_cu(EXACT, ALPHA1, !(s.ldw == s.W && s.st_nsegs == 1),
-                                                                  s.st_half != 0)) ? 1 : 0;
+            s.par_redo = grid_resident(grid, stream_blocks_per_cu<FRONT_INPAINT>(EXACT, ALPHA1, !(s.ldw == s.W && s.st_nsegs == 1),
+                                                                                 s.st_half != 0)) ? 1 : 0;
             if (!s.par_redo) return 0;
-            launch_stream(s, dim3(grid), st, EXACT, ALPHA1, !(s.ldw == s.W && s.st_nsegs == 1), s.st_half != 0);
+            launch_stream<FRONT_INPAINT>(s, dim3(grid), st, EXACT, ALPHA1, !(s.ldw == s.W && s.st_nsegs == 1), s.st_half != 0);
             rc = launch_check("tv_stream_kernel(redo)");
         }
         if (rc) return rc;
         if (hipMemsetAsync(a.redo, 0, sizeof(int), st) != hipSuccess) return launch_check("psgla_tv_step(redo clear)");
         return 0;
     }
+    // the stream / tile kernels run Langevin steps only (FRONT_INPAINT, FRONT_STEP_GIVEN); FS: the front whose
+    // instances this launch takes (never referenced for the bare prox, which has none)
+    constexpr int FS = FRONT == FRONT_GIVEN ? FRONT_INPAINT : FRONT;
     if (mask & 1) {
-        if (FRONT == FRONT_INPAINT && a.tile_r > 0) {
+        if (FRONT != FRONT_GIVEN && a.tile_r > 0) {
             TvArgs s = a;
             s.fin_inline = (mask & 2) ? 1 : 0;
             const int grid = P * s.nbands * s.st_nsegs;                   // tile_kernel: one workgroup per tile
@@ -177,17 +181,17 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
             // parallel early-stop redo when every tile is resident at once (its grid barrier); otherwise the
             // finalising workgroup recomputes stopped chains itself
             const bool gen = !(s.ldw == s.W && s.st_nsegs == 1);
-            s.par_redo = (s.redo && grid_resident(grid, tile_blocks_per_cu(s, EXACT, ALPHA1, gen))) ? 1 : 0;
-            if (launch_tile(s, dim3(grid), st, EXACT, ALPHA1, gen)) return launch_check("tv_tile_kernel");
+            s.par_redo = (s.redo && grid_resident(grid, tile_blocks_per_cu<FS>(s, EXACT, ALPHA1, gen))) ? 1 : 0;
+            if (launch_tile<FS>(s, dim3(grid), st, EXACT, ALPHA1, gen)) return launch_check("tv_tile_kernel");
             return fail(0, "psgla_tv_step: internal error: no tile kernel of this shape");
         }
-        if (FRONT == FRONT_INPAINT && a.stream) {
+        if (FRONT != FRONT_GIVEN && a.stream) {
             TvArgs s = a;
             s.fin_inline = (mask & 2) ? 1 : 0;
             const int grid = s.split_wgs > 0 ? s.split_wgs : s.st_nvp;   // virtual planes
             const bool gen = !(s.ldw == s.W && s.st_nsegs == 1);
-            s.par_redo = (s.redo && grid_resident(grid, stream_blocks_per_cu(EXACT, ALPHA1, gen, s.st_half != 0))) ? 1 : 0;
-            launch_stream(s, dim3(grid), st, EXACT, ALPHA1, gen, s.st_half != 0);
+            s.par_redo = (s.redo && grid_resident(grid, stream_blocks_per_cu<FS>(EXACT, ALPHA1, gen, s.st_half != 0))) ? 1 : 0;
+            launch_stream<FS>(s, dim3(grid), st, EXACT, ALPHA1, gen, s.st_half != 0);
             int rc = launch_check("tv_stream_kernel");
             if (rc) return rc;
             return 0;                    // finalised in-kernel (or main pass only)
@@ -238,8 +242,8 @@ static int select_step_kernel(const PsglaTvStep* d, TvArgs& a) {
         { g_sel_err = "psgla_tv_step: kernel_variant must be 0 (auto), 1 (band), 2 (stream) or 4 (tile)"; return -1; }
     if (d->stream_windows < 0 || d->stream_windows > 2)
         { g_sel_err = "psgla_tv_step: stream_windows must be 0, 1 or 2"; return -1; }
-    // small-batch tile kernel: forced (variant 4) or, in auto mode, when all tiles fit in one round
-    // on the CUs (a row stream would be mostly pipeline fill: strong scaling's 64/N chains per GPU)
+    // small-batch tile kernel: forced (variant 4) or, in auto mode, when its tiles fit in one or two rounds
+    // on the CUs, see below (a row stream would be mostly pipeline fill: strong scaling's 64/N chains per GPU)
     a.tile_r = 0;
     a.tile_nw = 16;
     int tile_segs = 0, tile_sw = 0;
@@ -250,7 +254,8 @@ static int select_step_kernel(const PsglaTvStep* d, TvArgs& a) {
         tile_segs = (a.ldw % 4 == 0 && d->n_tv >= 1) ? stream_segments(a.W, a.ldw, d->n_tv, &tile_sw) : 0;
         // Shipped tile instances (round 6: none spills a VGPR -- a spill inside a divergent region loses the inactive
         // lanes' values): 32-row tiles (16 waves x 2 rows) always, 48-row tiles (16 x 3) at alpha = 1
-        // only; the 72-row tiles (8 x 9) of rounds 4-5 are gone (12-16 chains take the row stream)
+        // only; the 72-row tiles (8 x 9) of rounds 4-5 are gone (12-16 chains at 256 x 256 run as two rounds of
+        // 48-row tiles, below)
         const bool alpha1 = d->x2[0] == nullptr;
         int bh2 = 0, nb2 = 0;
         const int wg3 = alpha1 ? tile_geometry(P, d->H, tile_segs, d->n_tv, 16, 3, &bh, &nb) : 0;
@@ -330,7 +335,9 @@ int psgla_tv_step(const PsglaTvStep* d, const PsglaSchedule* s, void* stream) {
     int rc = check_tv_common(d->B, d->C, d->H, d->W, d->n_tv);
     if (rc) return rc;
     const bool alpha1 = d->x2[0] == nullptr;
-    if (!d->x[0] || !d->x[1] || !d->u2[0] || !d->u2[1] || !d->y || !d->mask || !d->norms || !d->arrive ||
+    if (d->data_term != 0 && d->data_term != 1) return fail(0, "psgla_tv_step: data_term must be 0 (inpainting) or 1 (Y given)");
+    const bool given = d->data_term == 1;
+    if (!d->x[0] || !d->x[1] || !d->u2[0] || !d->u2[1] || !d->y || (!given && !d->mask) || !d->norms || !d->arrive ||
         !d->fresh)
         return fail(0, "psgla_tv_step: missing buffer");
     if (!alpha1 && !d->x2[1]) return fail(0, "psgla_tv_step: x2[1] missing");
@@ -359,11 +366,27 @@ int psgla_tv_step(const PsglaTvStep* d, const PsglaSchedule* s, void* stream) {
     a.samples = s->samples; a.samples_cap = s->samples_cap;
     a.blocks = s->blocks; a.blocks2 = s->blocks2; a.blocks_cap = s->blocks_cap;
     a.redo = d->redo;
+    if (given) {
+        // Y of this step, written by an earlier launch on the stream: one (C, H, ldw) block per chain.  The parallel
+        // redo would run inside the next step's launch, after that step's Y was computed from an X not yet
+        // corrected: the finaliser's serial recompute (which re-reads Y from the same buffer) is the only one.
+        if (d->redo) return fail(0, "psgla_tv_step: redo must be NULL with data_term 1 (the finaliser recomputes serially)");
+        const long long cs = (long long)d->C * d->H * a.ldw;
+        if (d->y_chain_stride != cs && !(d->B == 1 && d->y_chain_stride == 0))
+            return fail(0, "psgla_tv_step: data_term 1 needs y_chain_stride == C*H*ldw");
+        a.y_cs = cs;
+        a.mask = nullptr; a.m_cs = 0;
+    }
     if (d->launch_mask < 0 || d->launch_mask > 4) return fail(0, "psgla_tv_step: launch_mask must be 0 .. 4");
     if (select_step_kernel(d, a) < 0) return g_sel_err == g_err ? (int)hipErrorInvalidValue : fail(0, g_sel_err);
     hipStream_t st = (hipStream_t)stream;
     const int m = d->launch_mask;
-    if (d->exact || !tv_fast_constants(a))
+    const bool exact = d->exact || !tv_fast_constants(a);
+    if (given) {
+        if (exact) return alpha1 ? launch_tv<true, FRONT_STEP_GIVEN, true>(a, st, m) : launch_tv<true, FRONT_STEP_GIVEN, false>(a, st, m);
+        return alpha1 ? launch_tv<false, FRONT_STEP_GIVEN, true>(a, st, m) : launch_tv<false, FRONT_STEP_GIVEN, false>(a, st, m);
+    }
+    if (exact)
         return alpha1 ? launch_tv<true, FRONT_INPAINT, true>(a, st, m) : launch_tv<true, FRONT_INPAINT, false>(a, st, m);
     return alpha1 ? launch_tv<false, FRONT_INPAINT, true>(a, st, m) : launch_tv<false, FRONT_INPAINT, false>(a, st, m);
 }
@@ -372,6 +395,11 @@ int psgla_tv_step_kernel(const PsglaTvStep* d) {
     if (!d) return fail(0, "psgla_tv_step_kernel: null descriptor");
     const int rc = check_tv_common(d->B, d->C, d->H, d->W, d->n_tv);
     if (rc) return -1;
+    // (the same answer for both data terms: the thresholds were measured for inpainting only)
+    if (d->data_term != 0 && d->data_term != 1) {
+        fail(0, "psgla_tv_step_kernel: data_term must be 0 (inpainting) or 1 (Y given)");
+        return -1;
+    }
     TvArgs a;
     memset(&a, 0, sizeof(a));
     a.B = d->B; a.C = d->C; a.H = d->H; a.W = d->W;

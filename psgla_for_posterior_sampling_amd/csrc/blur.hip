@@ -19,6 +19,11 @@ namespace psgla {
 // mode).  The taps are kernel arguments (compile-time indices -> SGPR operands).
 // With Y != NULL the Langevin update Y = (X + c1 g) + c2 Z is fused (g is never stored; X is read
 // from the staged tile).
+// Row pitch (psgla_blur_langevin): rows of X, y, g / Y lie BlurArgs::ld >= W elements apart (the fused TV engine's
+// padded pitch); the circular wrap, the tiles and the noise quads are the image's (W), so the image columns do not
+// depend on the pitch, and the padding columns are neither read nor written (W % 4 == 0: 16-byte accesses stay
+// aligned because ld % 4 == 0; otherwise the element path).  X is X[0] at even step indices, X[1] at odd ones
+// (a wave-uniform select: a captured [stencil, TV step] pair replays at either ping-pong parity).
 // ---------------------------------------------------------------------------------------
 constexpr int BL_TH = 64, BL_TW = 64, BL_MAXL = 8, BL_THREADS = 256;
 constexpr int BL_MAXK = 2 * BL_MAXL + 1;
@@ -32,7 +37,7 @@ __host__ __device__ constexpr int bl_mr(int L) {
 }
 
 struct BlurArgs {
-    const float* X;
+    const float* X[2];                             // input at even / odd step indices (*d_step + off)
     const float* y;
     long long y_cs;
     float hconv[BL_MAXK * BL_MAXK];
@@ -42,6 +47,7 @@ struct BlurArgs {
     float* g;
     float* Y;
     int B, C, H, W;
+    int ld;                                        // row pitch of X, y, g, Y (>= W)
     float sigma2, inv_sigma2, c1, c2;
     unsigned long long seed;
     int chain0;
@@ -103,12 +109,13 @@ __global__ void __launch_bounds__(BL_THREADS, (L <= 4 ? PSGLA_BLUR_WPE : 1)) blu
     static_assert(TQ * TB == BL_THREADS, "A^T r pass: one block per thread");
     __shared__ __attribute__((aligned(16))) float xs[XHA * XS + 8];
     __shared__ __attribute__((aligned(16))) float rs[RHA * RS];
-    const int H = a.H, W = a.W;
-    const size_t HW = (size_t)H * W;
+    const int H = a.H, W = a.W, LD = a.ld;
+    const size_t HW = (size_t)H * LD;                 // plane pitch
     const bool vec = (W & 3) == 0;
     const bool dma = (L & 1) == 0 && vec;   // even l on a 4-aligned width: every staging chunk is one aligned 16-B run
     const int per_plane = a.tiles_x * a.tiles_y;
     const long long step = (a.d_step ? *a.d_step : 0LL) + a.off;
+    const float* const xin = __builtin_amdgcn_readfirstlane((int)(step & 1)) ? a.X[1] : a.X[0];
     // circular index without loops: one correction covers every offset an output uses when 2l <= n; tiny
     // planes (and the unused rows past a partial tile) take the exact modulo
     auto wrap = [](int v, int n) {
@@ -144,7 +151,7 @@ __global__ void __launch_bounds__(BL_THREADS, (L <= 4 ? PSGLA_BLUR_WPE : 1)) blu
         for (int m = 0; m < MR; ++m) {
             yv[m][0] = yv[m][1] = yv[m][2] = yv[m][3] = 0.f;
             if (p0 + m < BL_TH + 2 * L) {
-                const float* yrow = yp + (size_t)wrap(tl.i0 - L + p0 + m, H) * W;
+                const float* yrow = yp + (size_t)wrap(tl.i0 - L + p0 + m, H) * LD;
                 if (yvec) {
                     const float4 v = ld4(yrow + gj);
                     yv[m][0] = v.x; yv[m][1] = v.y; yv[m][2] = v.z; yv[m][3] = v.w;
@@ -160,14 +167,14 @@ __global__ void __launch_bounds__(BL_THREADS, (L <= 4 ? PSGLA_BLUR_WPE : 1)) blu
     // 4-column chunks: chunk n of the tile -> buf[4n].  LDS-DMA (no registers, all in flight at once) or,
     // for odd l / widths not a multiple of 4, element loads through registers.
     auto stage_x = [&](const Tile& tl, float* buf) {
-        const float* xp = a.X + (size_t)tl.plane * HW;
+        const float* xp = xin + (size_t)tl.plane * HW;
         if (dma) {
 #pragma unroll
             for (int it = 0; it < NXI; ++it) {
                 const int n = it * BL_THREADS + t;
                 if (n < XH * XQ) {
                     const int p = n / XQ, qq = n - p * XQ;
-                    glds16(xp + (size_t)wrap(tl.i0 - 2 * L + p, H) * W + wrap(tl.j0 - 2 * L + 4 * qq, W),
+                    glds16(xp + (size_t)wrap(tl.i0 - 2 * L + p, H) * LD + wrap(tl.j0 - 2 * L + 4 * qq, W),
                            &buf[4 * (it * BL_THREADS + 64 * wv)]);
                 }
             }
@@ -175,7 +182,7 @@ __global__ void __launch_bounds__(BL_THREADS, (L <= 4 ? PSGLA_BLUR_WPE : 1)) blu
         }
         for (int n = t; n < XH * XQ; n += BL_THREADS) {
             const int p = n / XQ, qq = n - p * XQ;
-            const float* rowp = xp + (size_t)wrap(tl.i0 - 2 * L + p, H) * W;
+            const float* rowp = xp + (size_t)wrap(tl.i0 - 2 * L + p, H) * LD;
             const int gj = tl.j0 - 2 * L + 4 * qq;
             float4 v;
             v.x = rowp[wrap(gj, W)]; v.y = rowp[wrap(gj + 1, W)];
@@ -237,7 +244,7 @@ __global__ void __launch_bounds__(BL_THREADS, (L <= 4 ? PSGLA_BLUR_WPE : 1)) blu
                 float gv[4];
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) gv[kk] = EXACT ? (-acc[m][kk]) / a.sigma2 : (-acc[m][kk]) * a.inv_sigma2;
-                const size_t e0 = (size_t)tl.c * HW + (size_t)i * W + j;   // element index within the chain
+                const size_t e0 = (size_t)tl.c * HW + (size_t)i * LD + j;   // element offset within the chain
                 const size_t o = (size_t)tl.b * a.C * HW + e0;
                 if (a.Y) {
                     float z[4];   // psgla noise v2: columns j .. j + 3 (j a multiple of 4) are one quad of the row
@@ -297,12 +304,13 @@ __global__ void __launch_bounds__(BL_THREADS, (L <= 4 ? 3 : 1)) blur_sep_kernel(
     constexpr int BBUF = (B1 * M1 > RB * MR ? B1 * M1 : RB * MR) * HS;
     __shared__ __attribute__((aligned(16))) float bufA[ABUF];
     __shared__ __attribute__((aligned(16))) float bufB[BBUF];
-    const int H = a.H, W = a.W;
-    const size_t HW = (size_t)H * W;
+    const int H = a.H, W = a.W, LD = a.ld;
+    const size_t HW = (size_t)H * LD;                 // plane pitch
     const bool vec = (W & 3) == 0;
     const bool dma = (L & 1) == 0 && vec;
     const int per_plane = a.tiles_x * a.tiles_y;
     const long long step = (a.d_step ? *a.d_step : 0LL) + a.off;
+    const float* const xin = __builtin_amdgcn_readfirstlane((int)(step & 1)) ? a.X[1] : a.X[0];
     auto wrap = [](int v, int n) {
         if ((unsigned)v < (unsigned)n) return v;
         const int r = v + (v < 0 ? n : -n);
@@ -320,7 +328,7 @@ __global__ void __launch_bounds__(BL_THREADS, (L <= 4 ? 3 : 1)) blur_sep_kernel(
     const int rem = tid - plane * per_plane, ty = rem / a.tiles_x, tx = rem - ty * a.tiles_x;
     const int b = plane / a.C, c = plane - b * a.C;
     const int i0 = ty * BL_TH, j0 = tx * BL_TW;
-    const float* xp = a.X + (size_t)plane * HW;
+    const float* xp = xin + (size_t)plane * HW;
     const float* yp = a.y + (size_t)b * a.y_cs + (size_t)c * HW;
     const int t = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -336,7 +344,7 @@ __global__ void __launch_bounds__(BL_THREADS, (L <= 4 ? 3 : 1)) blur_sep_kernel(
         for (int m = 0; m < MR; ++m) {
             yv[m][0] = yv[m][1] = yv[m][2] = yv[m][3] = 0.f;
             if (p0 + m < BL_TH + 2 * L) {
-                const float* yrow = yp + (size_t)wrap(i0 - L + p0 + m, H) * W;
+                const float* yrow = yp + (size_t)wrap(i0 - L + p0 + m, H) * LD;
                 if (yvec) {
                     const float4 v = ld4(yrow + gj);
                     yv[m][0] = v.x; yv[m][1] = v.y; yv[m][2] = v.z; yv[m][3] = v.w;
@@ -354,14 +362,14 @@ __global__ void __launch_bounds__(BL_THREADS, (L <= 4 ? 3 : 1)) blur_sep_kernel(
             const int n = it * BL_THREADS + t;
             if (n < XH * XQ) {
                 const int p = n / XQ, qq = n - p * XQ;
-                glds16(xp + (size_t)wrap(i0 - 2 * L + p, H) * W + wrap(j0 - 2 * L + 4 * qq, W),
+                glds16(xp + (size_t)wrap(i0 - 2 * L + p, H) * LD + wrap(j0 - 2 * L + 4 * qq, W),
                        &bufA[4 * (it * BL_THREADS + 64 * wv)]);
             }
         }
     } else {
         for (int n = t; n < XH * XQ; n += BL_THREADS) {
             const int p = n / XQ, qq = n - p * XQ;
-            const float* rowp = xp + (size_t)wrap(i0 - 2 * L + p, H) * W;
+            const float* rowp = xp + (size_t)wrap(i0 - 2 * L + p, H) * LD;
             const int gj = j0 - 2 * L + 4 * qq;
             float4 v;
             v.x = rowp[wrap(gj, W)]; v.y = rowp[wrap(gj + 1, W)];
@@ -458,20 +466,20 @@ __global__ void __launch_bounds__(BL_THREADS, (L <= 4 ? 3 : 1)) blur_sep_kernel(
         float gv[4];
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) gv[kk] = (-acc[m][kk]) * a.inv_sigma2;
-        const size_t e0 = (size_t)c * HW + (size_t)i * W + j;
+        const size_t e0 = (size_t)c * HW + (size_t)i * LD + j;
         const size_t o = (size_t)b * a.C * HW + e0;
         if (a.Y) {
             float z[4];   // psgla noise v2: columns j .. j + 3 (j a multiple of 4) are one quad of the row
             normal_quad(a.seed, (uint32_t)(a.chain0 + b), (uint32_t)step, TAG_LANGEVIN, noise_quad((size_t)c * H + i, j, W), z);
             if (vec) {
-                const float4 xv = ld4(a.X + o);
+                const float4 xv = ld4(xin + o);
                 *reinterpret_cast<float4*>(a.Y + o) =
                     make_float4((xv.x + a.c1 * gv[0]) + a.c2 * z[0], (xv.y + a.c1 * gv[1]) + a.c2 * z[1],
                                 (xv.z + a.c1 * gv[2]) + a.c2 * z[2], (xv.w + a.c1 * gv[3]) + a.c2 * z[3]);
             } else {
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
-                    if (j + kk < W) a.Y[o + kk] = (a.X[o + kk] + a.c1 * gv[kk]) + a.c2 * z[kk];
+                    if (j + kk < W) a.Y[o + kk] = (xin[o + kk] + a.c1 * gv[kk]) + a.c2 * z[kk];
                 }
             }
         } else if (vec) {
@@ -539,12 +547,14 @@ extern "C" int psgla_blur_set_separable(int32_t enable) {
     return 0;
 }
 
-int psgla_blur_grad(const float* X, const float* y, int64_t y_chain_stride, const float* hconv, const float* hcorr,
-                    int32_t l, float* g, float* Y, int32_t B, int32_t C, int32_t H, int32_t W, float sigma2,
-                    float c1, float c2, uint64_t seed, int32_t chain0, const int64_t* d_step, int64_t step_offset,
-                    int32_t exact, void* stream) {
-    if (!X || !y || !hconv || !hcorr || (!g && !Y) || B <= 0 || C <= 0 || H <= 0 || W <= 0)
-        return fail(0, "psgla_blur_grad: bad arguments");
+}  // extern "C"
+
+// the launch shared by psgla_blur_grad (contiguous rows, one input) and psgla_blur_langevin (row pitch ld, the input
+// chosen by the step's parity)
+static int blur_launch(const float* X_even, const float* X_odd, const float* y, int64_t y_chain_stride,
+                       const float* hconv, const float* hcorr, int32_t l, float* g, float* Y, int32_t B, int32_t C,
+                       int32_t H, int32_t W, int32_t ld, float sigma2, float c1, float c2, uint64_t seed,
+                       int32_t chain0, const int64_t* d_step, int64_t step_offset, int32_t exact, void* stream) {
     if (l < 0 || l > BL_MAXL) return fail(0, "psgla_blur_grad: blur half-width l outside [0, 8]");
     if ((long long)B * C > 65535) return fail(0, "psgla_blur_grad: more than 65535 planes in one launch");
     BlurArgs a;
@@ -553,8 +563,8 @@ int psgla_blur_grad(const float* X, const float* y, int64_t y_chain_stride, cons
     // the taps (HOST memory, like the scalars) travel as kernel arguments: SGPR operands
     memcpy(a.hconv, hconv, sizeof(float) * K * K);
     memcpy(a.hcorr, hcorr, sizeof(float) * K * K);
-    a.X = X; a.y = y; a.y_cs = y_chain_stride; a.g = g; a.Y = Y;
-    a.B = B; a.C = C; a.H = H; a.W = W; a.sigma2 = sigma2; a.inv_sigma2 = (float)(1.0 / (double)sigma2);
+    a.X[0] = X_even; a.X[1] = X_odd; a.y = y; a.y_cs = y_chain_stride; a.g = g; a.Y = Y;
+    a.B = B; a.C = C; a.H = H; a.W = W; a.ld = ld; a.sigma2 = sigma2; a.inv_sigma2 = (float)(1.0 / (double)sigma2);
     a.c1 = c1; a.c2 = c2; a.seed = seed; a.chain0 = chain0; a.d_step = (const long long*)d_step;
     a.off = step_offset;
     a.tiles_x = (W + BL_TW - 1) / BL_TW;
@@ -573,5 +583,29 @@ int psgla_blur_grad(const float* X, const float* y, int64_t y_chain_stride, cons
     return launch_check("blur_grad");
 }
 
+extern "C" {
+
+int psgla_blur_grad(const float* X, const float* y, int64_t y_chain_stride, const float* hconv, const float* hcorr,
+                    int32_t l, float* g, float* Y, int32_t B, int32_t C, int32_t H, int32_t W, float sigma2,
+                    float c1, float c2, uint64_t seed, int32_t chain0, const int64_t* d_step, int64_t step_offset,
+                    int32_t exact, void* stream) {
+    if (!X || !y || !hconv || !hcorr || (!g && !Y) || B <= 0 || C <= 0 || H <= 0 || W <= 0)
+        return fail(0, "psgla_blur_grad: bad arguments");
+    return blur_launch(X, X, y, y_chain_stride, hconv, hcorr, l, g, Y, B, C, H, W, W, sigma2, c1, c2, seed, chain0,
+                       d_step, step_offset, exact, stream);
+}
+
+int psgla_blur_langevin(const float* X_even, const float* X_odd, const float* y, int64_t y_chain_stride,
+                        const float* hconv, const float* hcorr, int32_t l, float* Y, int32_t B, int32_t C, int32_t H,
+                        int32_t W, int32_t ld, float sigma2, float c1, float c2, uint64_t seed, int32_t chain0,
+                        const int64_t* d_step, int64_t step_offset, int32_t exact, void* stream) {
+    if (!X_even || !X_odd || !y || !hconv || !hcorr || !Y || B <= 0 || C <= 0 || H <= 0 || W <= 0)
+        return fail(0, "psgla_blur_langevin: bad arguments");
+    if (ld == 0) ld = W;
+    if (ld < W || (ld != W && ld % 4 != 0))
+        return fail(0, "psgla_blur_langevin: ld must be 0, W, or a multiple of 4 >= W");
+    return blur_launch(X_even, X_odd, y, y_chain_stride, hconv, hcorr, l, nullptr, Y, B, C, H, W, ld, sigma2, c1, c2,
+                       seed, chain0, d_step, step_offset, exact, stream);
+}
 
 }  // extern "C"

@@ -90,7 +90,10 @@ constexpr float TV_INV_OPT = 0x1.faee42p-1f;   // fp32(1 / (double)fp32(1.01)), 
 constexpr float TV_SIG = 12.5f;                // fp32(1 / 0.01 / 8)
 constexpr float TV_RHO = 0x1.fd70a4p+0f;       // fp32(1.99)
 
-enum Front { FRONT_INPAINT = 0, FRONT_GIVEN = 1 };
+// FRONT_INPAINT: the fused step with the inpainting data term; FRONT_GIVEN: the stand-alone prox of a given tensor
+// (psgla_tv_prox: no ping-pong, no schedule); FRONT_STEP_GIVEN: the fused step whose Y an earlier launch produced
+// (PsglaTvStep.data_term 1: FRONT_INPAINT's whole epilogue, only the front differs -- Y is loaded through yobs)
+enum Front { FRONT_INPAINT = 0, FRONT_GIVEN = 1, FRONT_STEP_GIVEN = 2 };
 
 struct TvArgs {
     int B, C, H, W;
@@ -101,7 +104,7 @@ struct TvArgs {
     float* mean[2];
     float* sq[2];
     const float* yin;               // FRONT_GIVEN input
-    const float* yobs;              // observation
+    const float* yobs;              // observation (FRONT_STEP_GIVEN: this step's Y, row pitch ldw)
     long long y_cs;
     const uint8_t* mask;
     long long m_cs;
@@ -375,12 +378,13 @@ constexpr int tile_mst_rows(int nw, int r) { return nw * r < 56 ? nw * r : 56; }
 // kernel launchers (one translation unit each)
 template <bool EXACT, int FRONT, bool ALPHA1> void launch_band_main(const TvArgs& a, dim3 grid, hipStream_t st);
 template <bool EXACT, int FRONT, bool ALPHA1> void launch_band_finalise(const TvArgs& a, dim3 grid, hipStream_t st);
-void launch_stream(const TvArgs& a, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen, bool half);
-bool launch_tile(const TvArgs& a, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen);
+// (stream / tile: FRONT_INPAINT or FRONT_STEP_GIVEN, each front's instances in a translation unit of its own)
+template <int FRONT> void launch_stream(const TvArgs& a, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen, bool half);
+template <int FRONT> bool launch_tile(const TvArgs& a, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen);
 // workgroups of the instance launch_stream / launch_tile would run that one CU holds at once (the runtime's occupancy
 // query, cached per instance; 0 if unknown): the parallel early-stop redo's grid barrier needs the grid resident
-int stream_blocks_per_cu(bool exact, bool alpha1, bool gen, bool half);
-int tile_blocks_per_cu(const TvArgs& a, bool exact, bool alpha1, bool gen);
+template <int FRONT> int stream_blocks_per_cu(bool exact, bool alpha1, bool gen, bool half);
+template <int FRONT> int tile_blocks_per_cu(const TvArgs& a, bool exact, bool alpha1, bool gen);
 
 // cached hipOccupancyMaxActiveBlocksPerMultiprocessor of one kernel instance (slot: the instance's index)
 static inline int occupancy_cached(int* cache, int slot, const void* kernel, int threads) {

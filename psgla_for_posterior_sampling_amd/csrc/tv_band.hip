@@ -22,6 +22,7 @@ __device__ __forceinline__ void tv_tile(const TvArgs& a, int plane, int tile, in
     float4 (*urow)[WAVE] = sh.urow;
     float (*red)[TV_NW][2] = sh.red;
     constexpr int R = TV_R;
+    constexpr bool STEP = FRONT != FRONT_GIVEN;       // a Langevin step (FRONT_INPAINT, FRONT_STEP_GIVEN), not the bare prox
     const int lane = threadIdx.x & (WAVE - 1);
     const int w = threadIdx.x >> 6;
     const int H = a.H, W = a.W, C = a.C;
@@ -110,6 +111,21 @@ __device__ __forceinline__ void tv_tile(const TvArgs& a, int plane, int tile, in
                     } else {
 #pragma unroll
                         for (int k = 0; k < CPL; ++k) xs[k] = colok[k] ? x2in[base + k] : 0.f;
+                    }
+                }
+            } else if (FRONT == FRONT_STEP_GIVEN) {  // the step's Y is given (FRONT_GIVEN's load); x2 start as FRONT_INPAINT
+                const float* yb = a.yobs + (size_t)b * a.y_cs + (size_t)c * HW + (size_t)gi[r] * W + gj0;
+                const float* xsin = (fresh || ALPHA1) ? a.x[par_in] : a.x2[par_in];
+                if (vec) {
+                    const float4 v = ld4(yb);
+                    const float4 q = ld4(xsin + base);
+                    Yv[0] = v.x; Yv[1] = v.y; Yv[2] = v.z; Yv[3] = v.w;
+                    xs[0] = q.x; xs[1] = q.y; xs[2] = q.z; xs[3] = q.w;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < CPL; ++k) {
+                        Yv[k] = colok[k] ? yb[k] : 0.f;
+                        xs[k] = colok[k] ? xsin[base + k] : 0.f;
                     }
                 }
             } else {  // FRONT_GIVEN: standalone prox of a given tensor
@@ -266,18 +282,18 @@ __device__ __forceinline__ void tv_tile(const TvArgs& a, int plane, int tile, in
 #pragma unroll
         for (int k = 0; k < CPL; ++k) {
             // X = (1 - alpha) Y + alpha D(Y)  (restoration_algorithms.py:238); alpha == 1 gives D(Y) exactly
-            if (FRONT == FRONT_INPAINT && !ALPHA1)
+            if (STEP && !ALPHA1)
                 Xo[k] = (1.0f - a.alpha) * f4get(yrow, k) + a.alpha * x2[r][k];
             else
                 Xo[k] = x2[r][k];
         }
-        float* xout = (FRONT == FRONT_INPAINT) ? a.x[par_out] : a.x2[1];
+        float* xout = STEP ? a.x[par_out] : a.x2[1];
         float* u2out = a.u2[par_out];
         if (vec && colcore[0]) {
             st4(xout + base, Xo[0], Xo[1], Xo[2], Xo[3]);
             st4(u2out + 2 * base, u0[r][0], u1[r][0], u0[r][1], u1[r][1]);
             st4(u2out + 2 * base + 4, u0[r][2], u1[r][2], u0[r][3], u1[r][3]);
-            if (FRONT == FRONT_INPAINT && !ALPHA1)
+            if (STEP && !ALPHA1)
                 st4(a.x2[par_out] + base, x2[r][0], x2[r][1], x2[r][2], x2[r][3]);
         } else if (!vec) {
 #pragma unroll
@@ -286,10 +302,10 @@ __device__ __forceinline__ void tv_tile(const TvArgs& a, int plane, int tile, in
                 xout[base + k] = Xo[k];
                 u2out[2 * (base + k)] = u0[r][k];
                 u2out[2 * (base + k) + 1] = u1[r][k];
-                if (FRONT == FRONT_INPAINT && !ALPHA1) a.x2[par_out][base + k] = x2[r][k];
+                if (STEP && !ALPHA1) a.x2[par_out][base + k] = x2[r][k];
             }
         }
-        if (FRONT == FRONT_INPAINT) {
+        if (STEP) {
 #pragma unroll
             for (int k = 0; k < CPL; ++k) {
                 if (!colcore[k]) continue;
@@ -399,6 +415,8 @@ void launch_band_finalise(const TvArgs& a, dim3 grid, hipStream_t st) {
     template void launch_band_finalise<E, F, A>(const TvArgs&, dim3, hipStream_t);
 PSGLA_BAND(true, FRONT_INPAINT, true) PSGLA_BAND(true, FRONT_INPAINT, false) PSGLA_BAND(true, FRONT_GIVEN, true)
 PSGLA_BAND(false, FRONT_INPAINT, true) PSGLA_BAND(false, FRONT_INPAINT, false) PSGLA_BAND(false, FRONT_GIVEN, true)
+PSGLA_BAND(true, FRONT_STEP_GIVEN, true) PSGLA_BAND(true, FRONT_STEP_GIVEN, false)
+PSGLA_BAND(false, FRONT_STEP_GIVEN, true) PSGLA_BAND(false, FRONT_STEP_GIVEN, false)
 #undef PSGLA_BAND
 
 }  // namespace psgla

@@ -2,6 +2,12 @@
 // (library overview: psgla_common.hpp)
 #include "psgla_common.hpp"
 
+// The front this translation unit instantiates the kernel for: FRONT_INPAINT here, FRONT_STEP_GIVEN through
+// tv_stream_given.hip (which defines the macro and includes this file), so the two instance sets build in parallel.
+#ifndef PSGLA_STREAM_FRONT
+#define PSGLA_STREAM_FRONT FRONT_INPAINT
+#endif
+
 namespace psgla {
 
 
@@ -503,7 +509,9 @@ __device__ __forceinline__ void stage_loop(const TvArgs& a, StreamSharedT<A1>& s
 // pass and the rare early-stop recompute, each with its own register allocation.
 // GEN: the row pitch is not the image width (rows padded: W % 4 != 0) -- the last-column, norm
 // handling of such rows, compiled only into the kernels that need it
-template <bool EXACT, bool ALPHA1, bool GEN, bool HALF>
+// FRONT_STEP_GIVEN: the front's part 1 loads the row of this step's Y (PsglaTvStep.y with data_term 1) where the
+// inpainting front loads the observation; no mask DMA, no noise.
+template <bool EXACT, bool ALPHA1, bool GEN, bool HALF, int FRONT>
 __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA1>& sh, const RowMap& rm, const int n,
                                             const bool track, const long long step, const bool fresh) {
     const int lane = threadIdx.x & (WAVE - 1);
@@ -555,7 +563,8 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
         RowCursor rc_cur, rc_dma;
         cursor_init<GEN, HALF>(a, rm, rc_cur, min(fw, Q - 1));
         cursor_init<GEN, HALF>(a, rm, rc_dma, min(fw, Q - 1));
-        // part `part` of the loads of stream row q: 0 = X, 1 = y, 2 = u2 (two halves), 3 = mask (+ x2)
+        // part `part` of the loads of stream row q: 0 = X, 1 = y (FRONT_STEP_GIVEN: Y), 2 = u2 (two halves),
+        // 3 = mask (+ x2; FRONT_STEP_GIVEN: x2 only, nothing at alpha = 1)
         auto front_issue = [&](int part, int q, const RowCursor& rc) {
             const int rr = min(rc.r, H - 1);
             const int bi = (q >> 2) & 1;
@@ -573,7 +582,7 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
                 glds16(u2in + 2 * base + 4, sh.stUb(fw, q));
             } else {
                 if (!ALPHA1) glds16(x2in + base, sh.stX2(fw, q));
-                glds4(a.mask + rc.g.mbase + roff, &sh.fmk[fw][bi][0]);
+                if (FRONT == FRONT_INPAINT) glds4(a.mask + rc.g.mbase + roff, &sh.fmk[fw][bi][0]);
             }
         };
         // row fw's loads up front; afterwards the loads of row q + 4 are issued one part per
@@ -595,29 +604,35 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
                     gjf = g.f0 + CPL * lc;
                     okf = g.on && gjf < W;
                 }
-                // psgla noise v2: the lane's 4 columns (gjf a multiple of 4) are one quad of the row, for
-                // any W and independent of the row pitch
-                uint32_t c0 = noise_quad(g.rbase + (size_t)rc_cur.r, gjf, W), c1 = (uint32_t)step,
-                         c2 = TAG_LANGEVIN, c3 = (uint32_t)(a.seed >> 32);
-                philox4x32_10(c0, c1, c2, c3, (uint32_t)a.seed, (uint32_t)(a.chain0 + g.bb));
-                ph0 = c0; ph1 = c1; ph2 = c2; ph3 = c3;
+                if (FRONT == FRONT_INPAINT) {
+                    // psgla noise v2: the lane's 4 columns (gjf a multiple of 4) are one quad of the row, for
+                    // any W and independent of the row pitch
+                    uint32_t c0 = noise_quad(g.rbase + (size_t)rc_cur.r, gjf, W), c1 = (uint32_t)step,
+                             c2 = TAG_LANGEVIN, c3 = (uint32_t)(a.seed >> 32);
+                    philox4x32_10(c0, c1, c2, c3, (uint32_t)a.seed, (uint32_t)(a.chain0 + g.bb));
+                    ph0 = c0; ph1 = c1; ph2 = c2; ph3 = c3;
+                }
             }
             step_barrier();
             // ---- phase 1: Box-Muller pair 1; DMA part 1
             front_issue(1, q + 4, rc_dma);
-            box_muller(ph0, ph1, zn0, zn1);
+            if (FRONT == FRONT_INPAINT) box_muller(ph0, ph1, zn0, zn1);
             step_barrier();
             // ---- phase 2: Box-Muller pair 2; DMA part 2
             front_issue(2, q + 4, rc_dma);
-            box_muller(ph2, ph3, zn2, zn3);
+            if (FRONT == FRONT_INPAINT) box_muller(ph2, ph3, zn2, zn3);
             step_barrier();
             // ---- phase 3: data term of row q -> ring 0 / Y ring; DMA part 3 of row q + 4
             {
-                wait_vm<4>();   // row q's loads landed; parts 0-2 of row q + 4 may fly
+                // row q's loads landed; parts 0-2 of row q + 4 (X, y, two halves of u2: four DMAs, issued after
+                // every part of row q) may fly.  The count does not depend on part 3, so it holds for
+                // FRONT_STEP_GIVEN too, whose part 3 is one DMA (x2) or none (alpha = 1); the front waves issue
+                // no other vector-memory operation, and the redo pass runs this same code.
+                wait_vm<4>();
                 const int bi = (q >> 2) & 1;
                 const float4 fX = sh.stX(fw, q)[lane];
                 const float4 fYo = sh.stY(fw, q)[lane];
-                const uint32_t fMw = sh.fmk[fw][bi][lane];
+                const uint32_t fMw = FRONT == FRONT_INPAINT ? sh.fmk[fw][bi][lane] : 0u;
                 const float X[CPL] = {fX.x, fX.y, fX.z, fX.w};
                 const float yo[CPL] = {fYo.x, fYo.y, fYo.z, fYo.w};
                 const float mk[CPL] = {(float)(fMw & 0xFFu), (float)((fMw >> 8) & 0xFFu),
@@ -626,7 +641,9 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
                 float Yv[CPL];
 #pragma unroll
                 for (int k = 0; k < CPL; ++k) {
-                    if (EXACT) {
+                    if (FRONT != FRONT_INPAINT) {
+                        Yv[k] = okf ? yo[k] : 0.f;          // Y given (padding columns: 0, as below)
+                    } else if (EXACT) {
                         const float g = (-mk[k] * (X[k] - yo[k])) / a.sigma2;
                         Yv[k] = okf ? (X[k] + a.c1 * g) + a.c2 * Z[k] : 0.f;
                     } else {
@@ -824,7 +841,7 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
 // every stopped row once (HALF: each item of a pair alone, in both half-waves, as the serial recompute).  The
 // redone step's inputs are intact (ping-pong state).  (Folding the redo into the main pass's call site, in a loop,
 // measured +14 % per step: the loop keeps the row map live across the pipeline.)
-template <bool EXACT, bool ALPHA1, bool GEN, bool HALF>
+template <bool EXACT, bool ALPHA1, bool GEN, bool HALF, int FRONT>
 __device__ __forceinline__ void stream_redo(const TvArgs& a, StreamSharedT<ALPHA1>& sh, long long pstep, bool pfresh) {
     RowMap rm;
     build_rowmap(a, blockIdx.x, rm);
@@ -846,12 +863,12 @@ __device__ __forceinline__ void stream_redo(const TvArgs& a, StreamSharedT<ALPHA
             r1.lo0 = rm.lo(s);
             r1.lo1 = r1.lo2 = r1.lo3 = 0;
             __syncthreads();
-            stream_pass<EXACT, ALPHA1, GEN, HALF>(a, sh, r1, nstop, false, pstep, pfresh);
+            stream_pass<EXACT, ALPHA1, GEN, HALF, FRONT>(a, sh, r1, nstop, false, pstep, pfresh);
         }
     }
 }
 
-template <bool EXACT, bool ALPHA1, bool GEN, bool HALF>
+template <bool EXACT, bool ALPHA1, bool GEN, bool HALF, int FRONT>
 __global__ void __launch_bounds__(TV_THREADS) tv_stream_kernel(const TvArgs a) {
     __shared__ StreamSharedT<ALPHA1> sh;
     __shared__ int s_stop[MAXG];
@@ -860,19 +877,22 @@ __global__ void __launch_bounds__(TV_THREADS) tv_stream_kernel(const TvArgs a) {
     const long long step = launch_step(a);
     const bool fresh = launch_fresh(a);
     // the previous step's pending early-stop redo (rare): all workgroups in parallel, then one grid barrier;
-    // launch_mask 4 (redo_only): the redo alone
-    if (a.par_redo && (a.fin_inline || a.redo_only)) {
-        const int pend = __builtin_amdgcn_readfirstlane(a.redo[0]);
-        if (pend & 1) {
-            stream_redo<EXACT, ALPHA1, GEN, HALF>(a, sh, step - 1, (pend & 2) != 0);
-            if (!a.redo_only) grid_sync(a.redo + 1, a.arrive + 3);
+    // launch_mask 4 (redo_only): the redo alone.  (Not with FRONT_STEP_GIVEN: this launch's Y was computed from the X
+    // the redo would only now correct -- psgla_tv_step never sets par_redo there, the finaliser recomputes serially.)
+    if constexpr (FRONT == FRONT_INPAINT) {
+        if (a.par_redo && (a.fin_inline || a.redo_only)) {
+            const int pend = __builtin_amdgcn_readfirstlane(a.redo[0]);
+            if (pend & 1) {
+                stream_redo<EXACT, ALPHA1, GEN, HALF, FRONT>(a, sh, step - 1, (pend & 2) != 0);
+                if (!a.redo_only) grid_sync(a.redo + 1, a.arrive + 3);
+            }
+            if (a.redo_only) return;
         }
-        if (a.redo_only) return;
     }
     {
         RowMap rm;
         build_rowmap(a, blockIdx.x, rm);
-        stream_pass<EXACT, ALPHA1, GEN, HALF>(a, sh, rm, a.n_tv, true, step, fresh);
+        stream_pass<EXACT, ALPHA1, GEN, HALF, FRONT>(a, sh, rm, a.n_tv, true, step, fresh);
         if (!a.fin_inline) return;        // main-pass-only launch (kernel timing): no side effects
         // rel_err partial sums of this stream -> global, per segment's chain (deepinv's
         // early-stop test, per chain); the tracking stages wrote sh.red[segment][k - 1]
@@ -967,7 +987,7 @@ __global__ void __launch_bounds__(TV_THREADS) tv_stream_kernel(const TvArgs a) {
         // the virtual plane (plane, column segment); HALF: the item alone, in both half-waves
         plane_rowmap(a.H, HALF ? a.st_nvp + item : item, rm);
         const int nstop = __builtin_amdgcn_readfirstlane(s_stop[plane / C]);
-        stream_pass<EXACT, ALPHA1, GEN, HALF>(a, sh, rm, nstop, false, step, fresh);
+        stream_pass<EXACT, ALPHA1, GEN, HALF, FRONT>(a, sh, rm, nstop, false, step, fresh);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < a.B * a.n_tv * 2; i += blockDim.x) a.norms[i] = 0.0;
@@ -978,12 +998,13 @@ __global__ void __launch_bounds__(TV_THREADS) tv_stream_kernel(const TvArgs a) {
     }
 }
 
-int stream_blocks_per_cu(bool exact, bool alpha1, bool gen, bool half) {
+template <>
+int stream_blocks_per_cu<PSGLA_STREAM_FRONT>(bool exact, bool alpha1, bool gen, bool half) {
     static int cache[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
     const int slot = (exact ? 8 : 0) | (alpha1 ? 4 : 0) | (gen ? 2 : 0) | (half ? 1 : 0);
 #define PSGLA_STREAM_OCC(E, A, G, HF) \
     if (exact == E && alpha1 == A && gen == G && half == HF) \
-        return occupancy_cached(cache, slot, reinterpret_cast<const void*>(&tv_stream_kernel<E, A, G, HF>), TV_THREADS);
+        return occupancy_cached(cache, slot, reinterpret_cast<const void*>(&tv_stream_kernel<E, A, G, HF, PSGLA_STREAM_FRONT>), TV_THREADS);
     PSGLA_STREAM_OCC(true, true, false, false) PSGLA_STREAM_OCC(true, true, true, false) PSGLA_STREAM_OCC(true, false, false, false) PSGLA_STREAM_OCC(true, false, true, false)
     PSGLA_STREAM_OCC(false, true, false, false) PSGLA_STREAM_OCC(false, true, true, false) PSGLA_STREAM_OCC(false, false, false, false) PSGLA_STREAM_OCC(false, false, true, false)
     PSGLA_STREAM_OCC(true, true, true, true) PSGLA_STREAM_OCC(true, false, true, true) PSGLA_STREAM_OCC(false, true, true, true) PSGLA_STREAM_OCC(false, false, true, true)
@@ -991,9 +1012,10 @@ int stream_blocks_per_cu(bool exact, bool alpha1, bool gen, bool half) {
     return 0;
 }
 
-void launch_stream(const TvArgs& s, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen, bool half) {
+template <>
+void launch_stream<PSGLA_STREAM_FRONT>(const TvArgs& s, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen, bool half) {
 #define PSGLA_STREAM(E, A, G, HF) \
-    if (exact == E && alpha1 == A && gen == G && half == HF) { hipLaunchKernelGGL((tv_stream_kernel<E, A, G, HF>), grid, dim3(TV_THREADS), 0, st, s); return; }
+    if (exact == E && alpha1 == A && gen == G && half == HF) { hipLaunchKernelGGL((tv_stream_kernel<E, A, G, HF, PSGLA_STREAM_FRONT>), grid, dim3(TV_THREADS), 0, st, s); return; }
     PSGLA_STREAM(true, true, false, false) PSGLA_STREAM(true, true, true, false) PSGLA_STREAM(true, false, false, false) PSGLA_STREAM(true, false, true, false)
     PSGLA_STREAM(false, true, false, false) PSGLA_STREAM(false, true, true, false) PSGLA_STREAM(false, false, false, false) PSGLA_STREAM(false, false, true, false)
     PSGLA_STREAM(true, true, true, true) PSGLA_STREAM(true, false, true, true) PSGLA_STREAM(false, true, true, true) PSGLA_STREAM(false, false, true, true)

@@ -3,6 +3,12 @@
 // (library overview: psgla_common.hpp)
 #include "psgla_common.hpp"
 
+// The front this translation unit instantiates the kernel for: FRONT_INPAINT here, FRONT_STEP_GIVEN through
+// tv_tile_given.hip (which defines the macro and includes this file), so the two instance sets build in parallel.
+#ifndef PSGLA_TILE_FRONT
+#define PSGLA_TILE_FRONT FRONT_INPAINT
+#endif
+
 namespace psgla {
 
 // ---------------------------------------------------------------------------------------
@@ -37,7 +43,8 @@ struct TileShared {
 
 // before_u2: called by every wave once the tile's rel-err sums and X side are issued, before its u2 stores
 // (the kernel's main pass: the step's arrival, so the u2 stores drain while the last workgroup finalises)
-template <bool EXACT, bool ALPHA1, int R, bool GEN, int NW, typename BeforeU2>
+// FRONT_STEP_GIVEN: fY is this step's Y (PsglaTvStep.y with data_term 1): no mask loads, no noise.
+template <bool EXACT, bool ALPHA1, int R, bool GEN, int NW, int FRONT, typename BeforeU2>
 __device__ __forceinline__ void sb_tile(const TvArgs& a, TileShared<R, NW>& sh, int plane, int seg, int band, int n_it,
                                         bool track, long long step, bool fresh, BeforeU2&& before_u2) {
     float x2[R][CPL], u0[R][CPL], u1[R][CPL];
@@ -90,13 +97,18 @@ __device__ __forceinline__ void sb_tile(const TvArgs& a, TileShared<R, NW>& sh, 
                 if (!ALPHA1) fXS[r] = ld4(a.x2[par_in] + base);
             }
             fY[r] = ld4(a.yobs + (size_t)b * a.y_cs + (size_t)c * HW + (size_t)gi[r] * L + gj0);
-            fM[r] = *reinterpret_cast<const uint32_t*>(a.mask + (size_t)b * a.m_cs + (size_t)gi[r] * L + gj0);
+            if (FRONT == FRONT_INPAINT)
+                fM[r] = *reinterpret_cast<const uint32_t*>(a.mask + (size_t)b * a.m_cs + (size_t)gi[r] * L + gj0);
         }
     }
     // ---- 2. the noise of the tile's rows (no memory dependence: overlaps the loads)
     float Zn[R][CPL];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
+        if (FRONT != FRONT_INPAINT) {
+            Zn[r][0] = Zn[r][1] = Zn[r][2] = Zn[r][3] = 0.f;
+            continue;
+        }
         // psgla noise v2: the lane's 4 columns (from a multiple of 4) are one quad of the row, for any W and
         // independent of the row pitch
         normal_quad(a.seed, (uint32_t)(a.chain0 + b), (uint32_t)step, TAG_LANGEVIN,
@@ -116,7 +128,9 @@ __device__ __forceinline__ void sb_tile(const TvArgs& a, TileShared<R, NW>& sh, 
 #pragma unroll
         for (int k = 0; k < CPL; ++k) {
             float Y;
-            if (EXACT) {
+            if (FRONT != FRONT_INPAINT) {
+                Y = yo[k];
+            } else if (EXACT) {
                 const float g = (-mk[k] * (X[k] - yo[k])) / a.sigma2;
                 Y = (X[k] + a.c1 * g) + a.c2 * Zn[r][k];
             } else {
@@ -404,7 +418,7 @@ __device__ __forceinline__ void sb_tile(const TvArgs& a, TileShared<R, NW>& sh, 
     }
 }
 
-template <bool EXACT, bool ALPHA1, int R, bool GEN, int NW>
+template <bool EXACT, bool ALPHA1, int R, bool GEN, int NW, int FRONT>
 __global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
     __shared__ TileShared<R, NW> sh;
     constexpr bool SPLIT = NW == 8;                    // two-phase arrival (below)
@@ -425,8 +439,9 @@ __global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
         // The previous step's pending early-stop redo (rare; a.redo[0], published by that step's finaliser; round 5):
         // every workgroup whose chain stopped redoes its own tile of that step with the stopped iteration count
         // (the step's inputs are intact: ping-pong state), all in parallel, then one grid barrier before this
-        // step reads them.  launch_mask 4 (redo_only): the redo alone.
-        if (a.par_redo && (a.fin_inline || a.redo_only)) {
+        // step reads them.  launch_mask 4 (redo_only): the redo alone.  (Never with FRONT_STEP_GIVEN: this launch's Y
+        // was computed from the X the redo would only now correct; its finaliser recomputes serially.)
+        if (FRONT == FRONT_INPAINT && a.par_redo && (a.fin_inline || a.redo_only)) {
             const int pend = __builtin_amdgcn_readfirstlane(a.redo[0]);
             if (pend & 1) {
                 if (item < N) {
@@ -435,7 +450,7 @@ __global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
                     const int band = t - seg * a.nbands;
                     const int nstop = __builtin_amdgcn_readfirstlane(a.redo[4 + plane / a.C]);
                     if (nstop < a.n_tv)
-                        sb_tile<EXACT, ALPHA1, R, GEN, NW>(a, sh, plane, seg, band, nstop, false, step - 1,
+                        sb_tile<EXACT, ALPHA1, R, GEN, NW, FRONT>(a, sh, plane, seg, band, nstop, false, step - 1,
                                                            (pend & 2) != 0, [] {});
                 }
                 if (!a.redo_only) grid_sync(a.redo + 1, a.arrive + 3);
@@ -473,8 +488,8 @@ __global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
             const int plane = item / T, t = item - plane * T;
             const int seg = GEN ? t / a.nbands : 0;
             const int band = t - seg * a.nbands;
-            if constexpr (SPLIT) sb_tile<EXACT, ALPHA1, R, GEN, NW>(a, sh, plane, seg, band, a.n_tv, true, step, fresh, arrive);
-            else sb_tile<EXACT, ALPHA1, R, GEN, NW>(a, sh, plane, seg, band, a.n_tv, true, step, fresh, [] {});
+            if constexpr (SPLIT) sb_tile<EXACT, ALPHA1, R, GEN, NW, FRONT>(a, sh, plane, seg, band, a.n_tv, true, step, fresh, arrive);
+            else sb_tile<EXACT, ALPHA1, R, GEN, NW, FRONT>(a, sh, plane, seg, band, a.n_tv, true, step, fresh, [] {});
         }
         if (!SPLIT || item >= N) arrive();
     }
@@ -614,7 +629,7 @@ __global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
             const int band = t - seg * a.nbands;
             const int nstop = __builtin_amdgcn_readfirstlane(sh.s_stop[plane / a.C]);
             if (nstop < a.n_tv) {
-                sb_tile<EXACT, ALPHA1, R, GEN, NW>(a, sh, plane, seg, band, nstop, false, step, fresh, [] {});
+                sb_tile<EXACT, ALPHA1, R, GEN, NW, FRONT>(a, sh, plane, seg, band, nstop, false, step, fresh, [] {});
                 wait_vm0();
                 __syncthreads();
             }
@@ -635,24 +650,26 @@ __global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
     }
 }
 
-int tile_blocks_per_cu(const TvArgs& s, bool exact, bool alpha1, bool gen) {
+template <>
+int tile_blocks_per_cu<PSGLA_TILE_FRONT>(const TvArgs& s, bool exact, bool alpha1, bool gen) {
     static int cache[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
     const int slot = (exact ? 8 : 0) | (alpha1 ? 4 : 0) | (gen ? 2 : 0) | (s.tile_r == 3 ? 1 : 0);
 #define PSGLA_TILE_OCC(E, A, NWV, RV) \
     if (exact == E && alpha1 == A && s.tile_nw == NWV && s.tile_r == RV) \
-        return occupancy_cached(cache, slot, gen ? reinterpret_cast<const void*>(&tv_tile_kernel<E, A, RV, true, NWV>) \
-                                                 : reinterpret_cast<const void*>(&tv_tile_kernel<E, A, RV, false, NWV>), NWV * WAVE);
+        return occupancy_cached(cache, slot, gen ? reinterpret_cast<const void*>(&tv_tile_kernel<E, A, RV, true, NWV, PSGLA_TILE_FRONT>) \
+                                                 : reinterpret_cast<const void*>(&tv_tile_kernel<E, A, RV, false, NWV, PSGLA_TILE_FRONT>), NWV * WAVE);
     PSGLA_TILE_OCC(true, true, 16, 2) PSGLA_TILE_OCC(true, false, 16, 2) PSGLA_TILE_OCC(false, true, 16, 2) PSGLA_TILE_OCC(false, false, 16, 2)
     PSGLA_TILE_OCC(true, true, 16, 3) PSGLA_TILE_OCC(false, true, 16, 3)
 #undef PSGLA_TILE_OCC
     return 0;
 }
 
-bool launch_tile(const TvArgs& s, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen) {
+template <>
+bool launch_tile<PSGLA_TILE_FRONT>(const TvArgs& s, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen) {
 #define PSGLA_TILE(E, A, NWV, RV) \
     if (exact == E && alpha1 == A && s.tile_nw == NWV && s.tile_r == RV) { \
-        if (!gen) hipLaunchKernelGGL((tv_tile_kernel<E, A, RV, false, NWV>), grid, dim3(NWV * WAVE), 0, st, s); \
-        else hipLaunchKernelGGL((tv_tile_kernel<E, A, RV, true, NWV>), grid, dim3(NWV * WAVE), 0, st, s);      \
+        if (!gen) hipLaunchKernelGGL((tv_tile_kernel<E, A, RV, false, NWV, PSGLA_TILE_FRONT>), grid, dim3(NWV * WAVE), 0, st, s); \
+        else hipLaunchKernelGGL((tv_tile_kernel<E, A, RV, true, NWV, PSGLA_TILE_FRONT>), grid, dim3(NWV * WAVE), 0, st, s);      \
         return true; \
     }
     // the instances select_step_kernel (api.hip) dispatches -- none spills a VGPR (round 6; checked by

@@ -3,7 +3,9 @@
 ``FusedTvChains`` runs B independent PSGLA chains (inpainting fidelity + warm-started TV
 prox) with one fused kernel launch per Langevin step (the band kernel adds a small finaliser):
 restoration_algorithms.py:231-271 with the closures of sampling_images.py:295 and the
-deepinv TVDenoiser of sampling_images.py:138.  All step-dependent quantities (noise
+deepinv TVDenoiser of sampling_images.py:138.  With ``blur=BlurTerm(...)`` the data term is the
+deblurring one (sampling_images.py:329-338): per step the stencil kernel writes Y (Langevin update fused)
+and the same fused kernels run the step from that Y (PsglaTvStep.data_term 1).  All step-dependent quantities (noise
 counter, block coefficients, sample / block slots, ping-pong parity) are derived on the
 device from a step counter, so any number of steps can be captured once in a hipGraph
 (``torch.cuda.CUDAGraph``) and replayed.
@@ -11,6 +13,7 @@ device from a step counter, so any number of steps can be captured once in a hip
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -23,13 +26,24 @@ from . import hip_ops as K
 KERNEL_VARIANTS = {"auto": 0, "band": 1, "stream": 2, "tile": 4}
 
 
+class BlurTerm(NamedTuple):
+    """The deblurring data term of FusedTvChains: host taps (2l+1, 2l+1) of A and A^T (BlurFidelity.taps_conv /
+    taps_corr), the half-width l, fp32 sigma2, and whether the stencil runs in its exact (tap-order) mode."""
+    taps_conv: np.ndarray
+    taps_corr: np.ndarray
+    l: int
+    sigma2: float
+    exact: bool = False
+
+
 class FusedTvChains:
-    def __init__(self, init: torch.Tensor, y: torch.Tensor, mask_u8: torch.Tensor, *, c1: float, c2: float,
+    def __init__(self, init: torch.Tensor, y: torch.Tensor, mask_u8: torch.Tensor | None, *, c1: float, c2: float,
                  sigma2: float, alpha: float, ths: float, tv: K.TvConstants, seed: int, n_iter: int,
                  n_inter: int, n_inter_mmse: int, chain0: int = 0, exact: bool = False,
                  tv_x2: torch.Tensor | None = None, tv_u2: torch.Tensor | None = None,
                  store_samples: bool = True, store_blocks: bool = True, kernel_variant: str = "auto",
-                 stream_wgs: int = 0, stream_windows: str = "auto", parallel_redo: bool = True):
+                 stream_wgs: int = 0, stream_windows: str = "auto", parallel_redo: bool = True,
+                 blur: BlurTerm | None = None):
         if init.dim() != 4:
             raise ValueError("init must be (B, C, H, W)")
         if tv.n_it > N.TV_MAX_FUSED_IT:
@@ -61,7 +75,16 @@ class FusedTvChains:
             self.x2[0][..., :Wd].copy_(tv_x2)
             self.u2[0][..., :Wd, :].copy_(tv_u2)
         self.y = self._padded(y)
-        self.mask = self._padded(mask_u8)
+        self.blur = blur
+        if blur is None:
+            self.mask = self._padded(mask_u8)
+        else:
+            # deblurring: the stencil kernel writes each step's Y here, the fused step reads it (data_term 1); after
+            # step i it still holds Y_i (Y_prev)
+            self.mask = None
+            self.Ybuf = torch.zeros(self.pshape, **f32)
+            self.c1, self.c2 = float(c1), float(c2)
+            self.seed, self.chain0 = int(seed), int(chain0)
         self.sched = K.Schedule(self.pshape, n_iter, n_inter, n_inter_mmse, dev, store_samples, store_blocks)
         # rel-err partial sums spread over 8 copies (one per XCD) for the tile kernel: one image's 246 tiles
         # no longer queue on the same 16 atomics (castle B = 1: DESIGN.md 3.1b)
@@ -80,10 +103,15 @@ class FusedTvChains:
             d.mean[i] = self.mean[i].data_ptr()
             d.sq[i] = self.sq[i].data_ptr()
             d.x2[i] = self.x2[i].data_ptr() if (self.x2 is not None and not self.alpha1) else None
-        d.y = K._ptr(self.y, name="y")
-        d.y_chain_stride = 0 if self.y.shape[0] == 1 else C * H * self.ldw
-        d.mask = K._ptr(self.mask, torch.uint8, "mask")
-        d.mask_chain_stride = 0 if (self.mask.dim() == 2 or self.mask.shape[0] == 1) else H * self.ldw
+        if blur is None:
+            d.y = K._ptr(self.y, name="y")
+            d.y_chain_stride = 0 if self.y.shape[0] == 1 else C * H * self.ldw
+            d.mask = K._ptr(self.mask, torch.uint8, "mask")
+            d.mask_chain_stride = 0 if (self.mask.dim() == 2 or self.mask.shape[0] == 1) else H * self.ldw
+        else:
+            d.data_term = 1
+            d.y = K._ptr(self.Ybuf, name="Y")
+            d.y_chain_stride = C * H * self.ldw
         d.c1, d.c2, d.sigma2, d.alpha = c1, c2, sigma2, self.alpha
         d.tau, d.one_plus_tau, d.sigma_tv, d.rho = tv.tau, tv.one_plus_tau, tv.sigma_tv, tv.rho
         d.ths = float(np.float32(ths))
@@ -104,7 +132,9 @@ class FusedTvChains:
         d.stream_windows = {"auto": 0, "whole": 1, "half": 2}[stream_windows]
         # deepinv's early stop, when it fires, is redone in parallel by the next launch (include/psgla_hip.h); the
         # last step's pending redo is settled (launch_mask 4) before results are read: settle()
-        d.redo = self.work.redo.data_ptr() if parallel_redo else None
+        # (not with the deblurring data term: the next launch's Y is computed before a redo could correct X, so
+        # the step's finaliser recomputes stopped chains itself and settle() has nothing to do)
+        d.redo = self.work.redo.data_ptr() if (parallel_redo and blur is None) else None
         self.desc = d
         self._unsettled = False
         self.sched_struct = self.sched.struct(True, 0)
@@ -132,7 +162,13 @@ class FusedTvChains:
         return t[..., :self.W, :] if u2 else t[..., :self.W]
 
     # -- stepping -----------------------------------------------------------------
-    def _launch(self, desc):
+    def _launch(self, desc, stencil: bool = True):
+        if self.blur is not None and stencil:
+            # Y of the current step from its input X (x[step & 1], chosen on the device by the step's parity)
+            bl = self.blur
+            K.blur_langevin_pitched(self.x[0], self.x[1], self.y, bl.taps_conv, bl.taps_corr, bl.l, bl.sigma2,
+                                    self.c1, self.c2, self.seed, self.chain0, 0, self.Ybuf, self.W, exact=bl.exact,
+                                    d_step=self.sched.d_step)
         N.check(N.lib().psgla_tv_step(ctypes.byref(desc), ctypes.byref(self.sched_struct), K._stream()),
                 "psgla_tv_step")
 
@@ -165,7 +201,7 @@ class FusedTvChains:
 
     def capture(self, steps_per_graph: int):
         """Capture `steps_per_graph` identical steps into one hipGraph (after step 0): one launch per
-        step."""
+        step (deblurring: the stencil and the step)."""
         if self.steps_done == 0 and self.warm_first:
             self.step(1)
         s = torch.cuda.Stream(device=self.device)
@@ -250,8 +286,8 @@ class FusedTvChains:
         self.settle()
         d = N.PsglaTvStep.from_buffer_copy(self.desc)
         d.launch_mask = 1
-        for _ in range(n):
-            self._launch(d)
+        for i in range(n):
+            self._launch(d, stencil=i == 0)     # (deblurring: the step's Y once, then the TV kernel alone)
 
     def run(self, n: int | None = None, graph_steps: int = 0):
         n = self.n_iter - self.steps_done if n is None else n
@@ -289,6 +325,13 @@ class FusedTvChains:
         if step == self.steps_done:
             self.settle()           # the last step's output: a pending early-stop redo rewrites it
         return self._view(self.x[step & 1])
+
+    @property
+    def Y_prev(self) -> torch.Tensor:
+        """Deblurring: Y_i of the last step run (the buffer the next step's stencil overwrites)."""
+        if self.blur is None:
+            raise AttributeError("Y_prev: only the deblurring data term keeps each step's Y")
+        return self._view(self.Ybuf)
 
     @property
     def u2_state(self) -> torch.Tensor:

@@ -8,6 +8,9 @@ samples every ``n_inter`` steps, block means of X and of X**2) and error behavio
 Dispatch:
 * ``data_grad`` an :class:`InpaintingFidelity` and ``denoiser`` a :class:`TVDenoiser` ->
   the fused HIP step (one kernel launch per Langevin step, hipGraph-replayed): config 2.
+* ``data_grad`` a :class:`BlurFidelity` and ``denoiser`` a :class:`TVDenoiser` (``n_it_max`` <= 24) -> the same
+  engine and kernels, two launches per step (the stencil with the Langevin update fused writes Y, the fused step
+  runs from that Y), hipGraph-replayed; the stencil's ``exact`` defaults to ``data_grad.exact``.
 * a typed data term (:class:`InpaintingFidelity` / :class:`BlurFidelity`) and a PyTorch
   denoiser (DnCNN, DRUNet, any ``torch.nn.Module``) -> :class:`engine.DenoiserChains`: per step
   the denoiser forward on PyTorch-ROCm, then one HIP pass (inpainting: relaxation, accumulators
@@ -16,7 +19,8 @@ Dispatch:
   DnCNN / DRUNet, ``graph_steps`` steps are captured in one hipGraph and replayed: configs 3-4.
 * anything else (opaque closures) -> the closures are called as given, and the rest of the
   step (Gaussian noise, Langevin update, relaxation, accumulators, sample storage) runs as HIP
-  kernels; a ``BlurFidelity`` data term is fused with the Langevin update (one stencil kernel).
+  kernels; a ``BlurFidelity`` data term is fused with the Langevin update (one stencil kernel);
+  a :class:`TVDenoiser` with ``n_it_max`` > 24 runs here too (chunked prox).
 ``pnpula`` with a :class:`~denoisers.DenoiserPrior` prior and a typed data term runs
 :class:`engine.UlaChains` (hipGraph-replayed steps: config 5).
 The Gaussian noise is the in-kernel "psgla noise v2" stream of (seed, chain) instead of
@@ -35,7 +39,7 @@ import torch
 
 from . import hip_ops as K
 from .denoisers import DenoiserPrior, DnCNN, DRUNet, TVDenoiser
-from .engine import DenoiserChains, FusedTvChains, UlaChains
+from .engine import BlurTerm, DenoiserChains, FusedTvChains, UlaChains
 from .fidelity import BlurFidelity, InpaintingFidelity
 
 DEFAULT_GRAPH_STEPS = int(os.environ.get("PSGLA_GRAPH_STEPS", "50"))
@@ -132,16 +136,21 @@ def psgla(init, data_grad, denoiser, alpha, lambd, sig_float=0.0055, delta=4e-5,
     if save_images_online:
         snaps = _Snapshots(path, name, {"n_iter": n_iter, "lambda": lambd, "delta": delta_t.to(dev)})
 
-    fused = (isinstance(data_grad, InpaintingFidelity) and isinstance(denoiser, TVDenoiser)
+    fused = (isinstance(data_grad, (InpaintingFidelity, BlurFidelity)) and isinstance(denoiser, TVDenoiser)
              and denoiser.n_it_max <= K.N.TV_MAX_FUSED_IT)
     if fused:
+        blur = None
+        if isinstance(data_grad, BlurFidelity):
+            blur = BlurTerm(data_grad.taps_conv, data_grad.taps_corr, data_grad.l, data_grad.sigma2,
+                            bool(data_grad.exact if exact is None else exact))
         if exact is None:
             exact = denoiser.exact
         warm = not denoiser.needs_restart(shape)
-        eng = FusedTvChains(X0, data_grad.y, data_grad.mask_u8, c1=c1, c2=c2, sigma2=data_grad.sigma2,
-                            alpha=alpha_f, ths=float(np.float32(sig_noised)), tv=denoiser.constants(), seed=seed,
-                            n_iter=n_iter, n_inter=n_inter, n_inter_mmse=n_inter_mmse, chain0=chain0,
-                            exact=exact, tv_x2=denoiser.x2 if warm else None, tv_u2=denoiser.u2 if warm else None)
+        eng = FusedTvChains(X0, data_grad.y, None if blur else data_grad.mask_u8, c1=c1, c2=c2,
+                            sigma2=data_grad.sigma2, alpha=alpha_f, ths=float(np.float32(sig_noised)),
+                            tv=denoiser.constants(), seed=seed, n_iter=n_iter, n_inter=n_inter,
+                            n_inter_mmse=n_inter_mmse, chain0=chain0, exact=exact,
+                            tv_x2=denoiser.x2 if warm else None, tv_u2=denoiser.u2 if warm else None, blur=blur)
 
         def run_fused(n):
             eng.run(n, graph_steps=graph_steps if n >= 2 * graph_steps else 0)
@@ -150,6 +159,9 @@ def psgla(init, data_grad, denoiser, alpha, lambd, sig_float=0.0055, delta=4e-5,
             run_fused(n_iter)
         else:
             def snap(i):
+                if blur is not None:    # deblurring: the engine's Y buffer still holds Y_i
+                    snaps.save(i, eng.X, eng.Y_prev, eng.lists())
+                    return
                 # Y_i of the step just run, recomputed from its input X_i (still in the ping-pong buffer)
                 Xi = eng.input_state(i).contiguous()
                 Yi = K.langevin_update(Xi, K.inpaint_grad(Xi, data_grad.y, data_grad.mask_u8, data_grad.sigma2),
