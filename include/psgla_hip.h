@@ -73,9 +73,9 @@ typedef struct PsglaSchedule {
  * is honoured, `fresh` is cleared and *d_step advanced once the step is complete.
  * What is launched depends on the variant the shape selects (kernel_variant 0):
  *   - the small-batch tile kernel (tv_tile_kernel: any W, rows padded to the pitch ldw and cut
- *     into the stream kernel's column segments when W > 256) when its 32-, 48- or 72-row tiles
- *     all fit on the CUs at once (few chains per GPU, or a few real-size images; two rounds of
- *     48-row tiles for segmented rows): ONE launch of at most 32767 tiles; its last workgroup
+ *     into the stream kernel's column segments when W > 256) when its 32- or 48-row tiles
+ *     fit on the CUs in one or two rounds (few chains per GPU, or a few real-size images): ONE
+ *     launch of at most 32767 tiles; its last workgroup
  *     to arrive evaluates the early stop, recomputes stopped chains and advances the step (no
  *     second kernel);
  *   - else the row-streaming kernel (tv_stream_kernel: row pitch ldw % 4 == 0,

@@ -84,18 +84,18 @@ static int choose_split(long long P, int H, int h, int req, int* out) {
     return 0;
 }
 
-// Small-batch tile kernel geometry: NW waves of R rows (tile = NW R rows incl. n_tv halo rows at cuts
-// inside a plane), equal bands per plane, nsegs column segments (stream_segments); a band's core rows
-// stay within the LDS staging of mean / sq (tile_mst_rows).  Returns the number of workgroups (one per tile),
-// 0 if the shape does not fit (halo too large, no segmentation).
-static int tile_geometry(int P, int H, int nsegs, int h, int NW, int R, int* band_h, int* nbands) {
+// Small-batch tile kernel geometry: TV_NW waves of R rows (tile = TV_NW R rows incl. n_tv halo rows at cuts
+// inside a plane), equal bands per plane, nsegs column segments (stream_segments); the kernel stages mean / sq
+// of every row of the tile in LDS.  Returns the number of workgroups (one per tile), 0 if the shape does not fit
+// (halo too large, no segmentation).
+static int tile_geometry(int P, int H, int nsegs, int h, int R, int* band_h, int* nbands) {
     if (nsegs < 1 || R < 2) return 0;
-    const int rows = NW * R, mst = tile_mst_rows(NW, R);
+    const int rows = TV_NW * R;
     int nb, bh;
-    if (H <= mst) {
+    if (H <= rows) {
         nb = 1; bh = H;
     } else {
-        const int core = min(rows - 2 * h, mst);
+        const int core = rows - 2 * h;
         if (core < 1) return 0;
         nb = (H + core - 1) / core;
         bh = (H + nb - 1) / nb;
@@ -147,7 +147,7 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
         if (a.tile_r > 0) {
             const int grid = P * s.nbands * s.st_nsegs;
             const bool gen = !(s.ldw == s.W && s.st_nsegs == 1);
-            s.par_redo = grid_resident(grid, tile_blocks_per_cu<FRONT_INPAINT>(s, EXACT, ALPHA1, gen)) ? 1 : 0;
+            s.par_redo = grid_resident(grid, tile_blocks_per_cu<FRONT_INPAINT>(EXACT, ALPHA1, gen, s.tile_r)) ? 1 : 0;
             if (!s.par_redo) return 0;   // (the tile kernel's finaliser recomputed stopped chains itself)
             if (!launch_tile<FRONT_INPAINT>(s, dim3(grid), st, EXACT, ALPHA1, gen))
                 return fail(0, "psgla_tv_step: internal error: no tile kernel of this shape");
@@ -172,7 +172,8 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
             TvArgs s = a;
             s.fin_inline = (mask & 2) ? 1 : 0;
             const int grid = P * s.nbands * s.st_nsegs;                   // tile_kernel: one workgroup per tile
-            // (the two-phase arrival counter keeps a count of workgroups in 15 bits)
+            // (the arrival word packs two 16-bit counts, workgroups arrived and tiles that leave a stop possible; the
+            // high one is added as unc << 16 into a signed int, so both stay below 2^15)
             if (grid > 32767) return fail(0, "psgla_tv_step: more than 32767 tiles in one launch");
             // several copies of the rel-err sums only where many tiles share a chain: with the finaliser's copy
             // reads issued back to back (round 4), 8 copies cost 8 chains of 30 tiles +1.6 % and save castle at
@@ -181,7 +182,7 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
             // parallel early-stop redo when every tile is resident at once (its grid barrier); otherwise the
             // finalising workgroup recomputes stopped chains itself
             const bool gen = !(s.ldw == s.W && s.st_nsegs == 1);
-            s.par_redo = (s.redo && grid_resident(grid, tile_blocks_per_cu<FS>(s, EXACT, ALPHA1, gen))) ? 1 : 0;
+            s.par_redo = (s.redo && grid_resident(grid, tile_blocks_per_cu<FS>(EXACT, ALPHA1, gen, s.tile_r))) ? 1 : 0;
             if (launch_tile<FS>(s, dim3(grid), st, EXACT, ALPHA1, gen)) return launch_check("tv_tile_kernel");
             return fail(0, "psgla_tv_step: internal error: no tile kernel of this shape");
         }
@@ -245,7 +246,6 @@ static int select_step_kernel(const PsglaTvStep* d, TvArgs& a) {
     // small-batch tile kernel: forced (variant 4) or, in auto mode, when its tiles fit in one or two rounds
     // on the CUs, see below (a row stream would be mostly pipeline fill: strong scaling's 64/N chains per GPU)
     a.tile_r = 0;
-    a.tile_nw = 16;
     int tile_segs = 0, tile_sw = 0;
     if (d->kernel_variant == 4 || d->kernel_variant == 0) {
         const int P = d->B * d->C;
@@ -258,8 +258,8 @@ static int select_step_kernel(const PsglaTvStep* d, TvArgs& a) {
         // 48-row tiles, below)
         const bool alpha1 = d->x2[0] == nullptr;
         int bh2 = 0, nb2 = 0;
-        const int wg3 = alpha1 ? tile_geometry(P, d->H, tile_segs, d->n_tv, 16, 3, &bh, &nb) : 0;
-        const int wg2 = tile_geometry(P, d->H, tile_segs, d->n_tv, 16, 2, &bh2, &nb2);
+        const int wg3 = alpha1 ? tile_geometry(P, d->H, tile_segs, d->n_tv, 3, &bh, &nb) : 0;
+        const int wg2 = tile_geometry(P, d->H, tile_segs, d->n_tv, 2, &bh2, &nb2);
         if (d->kernel_variant == 4 && wg3 == 0 && wg2 == 0) { g_sel_err = "psgla_tv_step: shape not supported by the tile kernel"; return -1; }
         // auto: the tiles fit in one or two rounds on the CUs (measured: castle-size images at B = 3-4 and 321 x 481 at
         // B = 4-6 run faster as two rounds of tiles, profiles/r03l_tile_threshold.txt; since round 6, without the
@@ -277,7 +277,6 @@ static int select_step_kernel(const PsglaTvStep* d, TvArgs& a) {
                 a.band_h = bh2;
                 a.nbands = nb2;
             }
-            a.tile_nw = 16;
             // 32-row tiles (2 rows per wave) when they still fit in one round: one or a few images leave most
             // CUs idle at 48 rows (castle B = 1: 114 tiles of 48 rows vs 246 of 32 rows, 41.1 -> 35.0 us,
             // profiles/r03q_tile_r2_ab.txt); more tiles but shorter waves

@@ -144,7 +144,6 @@ struct TvArgs {
     int st_nvp;                     // stream kernel virtual planes: (plane, segment) items, or pairs of them (st_half)
     int fin_inline;                 // stream kernel: 1 = the last workgroup finalises the step
     int tile_r;                     // > 0: small-batch tile kernel with tile_r rows per wave (one tile per workgroup)
-    int tile_nw;                    // tile kernel: waves per workgroup (16 or 8)
     int norm_copies;                // tile kernel: copies of norms its rel-err sums are spread over (>= 1)
     int* redo;                      // stream / tile kernel: parallel early-stop redo state (PsglaTvStep.redo) or null
     int par_redo;                   // 1: the redo runs in parallel in the next launch (grid resident at once)
@@ -371,10 +370,6 @@ __device__ __forceinline__ StepInfo step_info(const TvArgs& a, long long step, c
     return si;
 }
 
-// Core rows whose mean / sq rows a tile stages in LDS: all rows of the tile, at most 56 (112 KB; a 72-row tile
-// of 8 waves x 9 rows has 52 core rows at n_tv = 10 -- tile_geometry keeps band_h within this)
-constexpr int tile_mst_rows(int nw, int r) { return nw * r < 56 ? nw * r : 56; }
-
 // kernel launchers (one translation unit each)
 template <bool EXACT, int FRONT, bool ALPHA1> void launch_band_main(const TvArgs& a, dim3 grid, hipStream_t st);
 template <bool EXACT, int FRONT, bool ALPHA1> void launch_band_finalise(const TvArgs& a, dim3 grid, hipStream_t st);
@@ -384,7 +379,7 @@ template <int FRONT> bool launch_tile(const TvArgs& a, dim3 grid, hipStream_t st
 // workgroups of the instance launch_stream / launch_tile would run that one CU holds at once (the runtime's occupancy
 // query, cached per instance; 0 if unknown): the parallel early-stop redo's grid barrier needs the grid resident
 template <int FRONT> int stream_blocks_per_cu(bool exact, bool alpha1, bool gen, bool half);
-template <int FRONT> int tile_blocks_per_cu(const TvArgs& a, bool exact, bool alpha1, bool gen);
+template <int FRONT> int tile_blocks_per_cu(bool exact, bool alpha1, bool gen, int tile_r);
 
 // cached hipOccupancyMaxActiveBlocksPerMultiprocessor of one kernel instance (slot: the instance's index)
 static inline int occupancy_cached(int* cache, int slot, const void* kernel, int threads) {

@@ -8,7 +8,7 @@ namespace psgla {
 // ---------------------------------------------------------------------------------------
 // The fused tile: load -> Y -> n_it TV iterations in registers -> store core.
 // ---------------------------------------------------------------------------------------
-struct TvShared {
+struct BandShared {
     float ylds[TV_ROWS][TV_COLS];     // Y of the tile (prox anchor; tau*Y enters every iteration)
     float4 zrow[TV_NW][WAVE];         // first-row z of each wave (read by the wave above)
     float4 urow[TV_NW][WAVE];         // last-row u2[...,0] of each wave (read by the wave below)
@@ -16,8 +16,8 @@ struct TvShared {
 };
 
 template <bool EXACT, int FRONT, bool ALPHA1>
-__device__ __forceinline__ void tv_tile(const TvArgs& a, int plane, int tile, int n_it, bool track,
-                                        long long step, bool fresh, TvShared& sh) {
+__device__ __forceinline__ void band_tile(const TvArgs& a, int plane, int tile, int n_it, bool track,
+                                        long long step, bool fresh, BandShared& sh) {
     float4 (*zrow)[WAVE] = sh.zrow;
     float4 (*urow)[WAVE] = sh.urow;
     float (*red)[TV_NW][2] = sh.red;
@@ -320,7 +320,7 @@ __device__ __forceinline__ void tv_tile(const TvArgs& a, int plane, int tile, in
 
 template <bool EXACT, int FRONT, bool ALPHA1>
 __global__ void __launch_bounds__(TV_THREADS) tv_main_kernel(const TvArgs a) {
-    __shared__ TvShared sh;
+    __shared__ BandShared sh;
     const long long step = (a.d_step ? *a.d_step : 0LL) + a.step_offset;
     const bool fresh = a.fresh_dev ? (*a.fresh_dev != 0) : (a.fresh_host != 0);
     const int P = a.B * a.C;
@@ -333,7 +333,7 @@ __global__ void __launch_bounds__(TV_THREADS) tv_main_kernel(const TvArgs a) {
     const int plane = (k / T) * 8 + xcd;
     const int tile = k - (k / T) * T;
     if (plane >= P) return;
-    tv_tile<EXACT, FRONT, ALPHA1>(a, plane, tile, a.n_tv, true, step, fresh, sh);
+    band_tile<EXACT, FRONT, ALPHA1>(a, plane, tile, a.n_tv, true, step, fresh, sh);
 }
 
 // Early-stop finaliser (deepinv: break when rel_err < tol at inner iteration >= 2): recompute
@@ -341,7 +341,7 @@ __global__ void __launch_bounds__(TV_THREADS) tv_main_kernel(const TvArgs a) {
 // workspace, clear the restart flag and advance the step counter (last block to arrive).
 template <bool EXACT, int FRONT, bool ALPHA1>
 __global__ void __launch_bounds__(TV_THREADS) tv_finalise_kernel(const TvArgs a) {
-    __shared__ TvShared sh;
+    __shared__ BandShared sh;
     __shared__ int s_stop[MAXG];
     __shared__ int s_flag;
     const long long step = (a.d_step ? *a.d_step : 0LL) + a.step_offset;
@@ -380,7 +380,7 @@ __global__ void __launch_bounds__(TV_THREADS) tv_finalise_kernel(const TvArgs a)
         for (int item = blockIdx.x; item < P * T; item += gridDim.x) {
             const int plane = item / T, tile = item - (item / T) * T;
             const int g = a.per_chain_norm ? plane / a.C : 0;
-            if (s_stop[g] < a.n_tv) tv_tile<EXACT, FRONT, ALPHA1>(a, plane, tile, s_stop[g], false, step, fresh, sh);
+            if (s_stop[g] < a.n_tv) band_tile<EXACT, FRONT, ALPHA1>(a, plane, tile, s_stop[g], false, step, fresh, sh);
         }
     }
     __syncthreads();

@@ -998,28 +998,36 @@ __global__ void __launch_bounds__(TV_THREADS) tv_stream_kernel(const TvArgs a) {
     }
 }
 
-template <>
-int stream_blocks_per_cu<PSGLA_STREAM_FRONT>(bool exact, bool alpha1, bool gen, bool half) {
-    static int cache[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+// The shipped instances of this unit's front, written once: the kernel of (exact, alpha1, gen, half) and its slot in
+// the occupancy cache, or a null kernel.  launch_stream launches this pointer and stream_blocks_per_cu asks the runtime
+// for the occupancy of the same one, so the answer that allows the parallel redo's grid barrier always describes the
+// kernel that runs.  (Half windows exist with column segments only: gen.)
+struct StreamInstance {
+    void (*kernel)(TvArgs);
+    int slot;
+};
+static StreamInstance stream_instance(bool exact, bool alpha1, bool gen, bool half) {
     const int slot = (exact ? 8 : 0) | (alpha1 ? 4 : 0) | (gen ? 2 : 0) | (half ? 1 : 0);
-#define PSGLA_STREAM_OCC(E, A, G, HF) \
-    if (exact == E && alpha1 == A && gen == G && half == HF) \
-        return occupancy_cached(cache, slot, reinterpret_cast<const void*>(&tv_stream_kernel<E, A, G, HF, PSGLA_STREAM_FRONT>), TV_THREADS);
-    PSGLA_STREAM_OCC(true, true, false, false) PSGLA_STREAM_OCC(true, true, true, false) PSGLA_STREAM_OCC(true, false, false, false) PSGLA_STREAM_OCC(true, false, true, false)
-    PSGLA_STREAM_OCC(false, true, false, false) PSGLA_STREAM_OCC(false, true, true, false) PSGLA_STREAM_OCC(false, false, false, false) PSGLA_STREAM_OCC(false, false, true, false)
-    PSGLA_STREAM_OCC(true, true, true, true) PSGLA_STREAM_OCC(true, false, true, true) PSGLA_STREAM_OCC(false, true, true, true) PSGLA_STREAM_OCC(false, false, true, true)
-#undef PSGLA_STREAM_OCC
-    return 0;
-}
-
-template <>
-void launch_stream<PSGLA_STREAM_FRONT>(const TvArgs& s, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen, bool half) {
 #define PSGLA_STREAM(E, A, G, HF) \
-    if (exact == E && alpha1 == A && gen == G && half == HF) { hipLaunchKernelGGL((tv_stream_kernel<E, A, G, HF, PSGLA_STREAM_FRONT>), grid, dim3(TV_THREADS), 0, st, s); return; }
+    if (exact == E && alpha1 == A && gen == G && half == HF) return {&tv_stream_kernel<E, A, G, HF, PSGLA_STREAM_FRONT>, slot};
     PSGLA_STREAM(true, true, false, false) PSGLA_STREAM(true, true, true, false) PSGLA_STREAM(true, false, false, false) PSGLA_STREAM(true, false, true, false)
     PSGLA_STREAM(false, true, false, false) PSGLA_STREAM(false, true, true, false) PSGLA_STREAM(false, false, false, false) PSGLA_STREAM(false, false, true, false)
     PSGLA_STREAM(true, true, true, true) PSGLA_STREAM(true, false, true, true) PSGLA_STREAM(false, true, true, true) PSGLA_STREAM(false, false, true, true)
 #undef PSGLA_STREAM
+    return {nullptr, 0};
+}
+
+template <>
+int stream_blocks_per_cu<PSGLA_STREAM_FRONT>(bool exact, bool alpha1, bool gen, bool half) {
+    static int cache[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+    const StreamInstance si = stream_instance(exact, alpha1, gen, half);
+    return si.kernel ? occupancy_cached(cache, si.slot, reinterpret_cast<const void*>(si.kernel), TV_THREADS) : 0;
+}
+
+template <>
+void launch_stream<PSGLA_STREAM_FRONT>(const TvArgs& s, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen, bool half) {
+    const StreamInstance si = stream_instance(exact, alpha1, gen, half);
+    if (si.kernel) hipLaunchKernelGGL(si.kernel, grid, dim3(TV_THREADS), 0, st, s);
 }
 
 }  // namespace psgla

@@ -29,23 +29,26 @@ namespace psgla {
 // interior cuts.
 // ---------------------------------------------------------------------------------------
 
-template <int R, int NW>
+template <int R>
 struct TileShared {
-    float4 zrow[NW][WAVE];             // first-row z of each wave (read by the wave above)
-    float4 urow[NW][WAVE];             // last-row u2[..., 0] of each wave (read by the wave below)
-    float4 mst[tile_mst_rows(NW, R)][2][WAVE];   // mean / sq of the tile's core rows (LDS-DMA after the data term)
-    float2 red[MAXIT][NW][4];          // rel_err partial sums per (iteration, wave, 16-lane row of the wave)
+    float4 zrow[TV_NW][WAVE];             // first-row z of each wave (read by the wave above)
+    float4 urow[TV_NW][WAVE];             // last-row u2[..., 0] of each wave (read by the wave below)
+    float4 mst[TV_NW * R][2][WAVE];    // mean / sq of the tile's core rows (LDS-DMA after the data term)
+    float2 red[MAXIT][TV_NW][4];          // rel_err partial sums per (iteration, wave, 16-lane row of the wave)
     int s_stop[MAXG];
     int s_flag, s_item, s_next;
     int s_uncert;                      // this tile's rel-err partials do not rule out a stop (below)
     int s_nuncert;                     // finaliser: tiles whose partials do not rule out a stop
 };
 
-// before_u2: called by every wave once the tile's rel-err sums and X side are issued, before its u2 stores
-// (the kernel's main pass: the step's arrival, so the u2 stores drain while the last workgroup finalises)
 // FRONT_STEP_GIVEN: fY is this step's Y (PsglaTvStep.y with data_term 1): no mask loads, no noise.
-template <bool EXACT, bool ALPHA1, int R, bool GEN, int NW, int FRONT, typename BeforeU2>
-__device__ __forceinline__ void sb_tile(const TvArgs& a, TileShared<R, NW>& sh, int plane, int seg, int band, int n_it,
+// before_u2: called before the u2 stores; every call site passes `[] {}`.  It is kept for the code it generates, not
+// for what it does: each call site's lambda type makes its sb_tile an instantiation of its own (with its own
+// `iteration` / `store_x_side` bodies for the inliner).  One shared instantiation computes the same bits but moved
+// the register allocation and schedule of every instance, and 481 x 321 at batch 1 measured +1.3 %
+// (profiles/r08a_tile_cleanup_ab.txt, leg nocb).
+template <bool EXACT, bool ALPHA1, int R, bool GEN, int FRONT, typename BeforeU2>
+__device__ __forceinline__ void sb_tile(const TvArgs& a, TileShared<R>& sh, int plane, int seg, int band, int n_it,
                                         bool track, long long step, bool fresh, BeforeU2&& before_u2) {
     float x2[R][CPL], u0[R][CPL], u1[R][CPL];
     double* const nrm = a.norms;
@@ -175,8 +178,9 @@ __device__ __forceinline__ void sb_tile(const TvArgs& a, TileShared<R, NW>& sh, 
     const int wr0 = e0 + w * R, wr1 = wr0 + R;
     // The X side of the core rows' outputs (X, x2, accumulators / block means, sample) is final after the
     // last primal update.  48-row tiles issue it before the last dual update, so these stores drain while
-    // it runs and only u2 waits for it (8 chains: 40.0 -> 38.8 us); the 32- and 72-row tiles measured
-    // +2.3 % / +0.5 % that way and store after the last dual (profiles/r03s_tile_early_store_ab.txt)
+    // it runs and only u2 waits for it (8 chains: 40.0 -> 38.8 us); the 32-row tiles measured +2.3 % that way
+    // (the 72-row tiles of rounds 4-5, since removed, +0.5 %) and store after the last dual
+    // (profiles/r03s_tile_early_store_ab.txt)
     constexpr bool EARLY_X = R == 3;
     auto store_x_side = [&]() {
         if (need_prev) wait_vm0();                     // this wave's mean / sq DMA landed
@@ -301,7 +305,7 @@ __device__ __forceinline__ void sb_tile(const TvArgs& a, TileShared<R, NW>& sh, 
         __syncthreads();
         if (LAST && EARLY_X) store_x_side();
         // dual: u = prox_sigma_g_conj(u2 + sigma nabla z, ths); u2 += rho (u - u2)
-        const float4 dn = (w < NW - 1) ? sh.zrow[w + 1][lane] : zero4;
+        const float4 dn = (w < TV_NW - 1) ? sh.zrow[w + 1][lane] : zero4;
         if (act_d) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -365,7 +369,7 @@ __device__ __forceinline__ void sb_tile(const TvArgs& a, TileShared<R, NW>& sh, 
         const int t = threadIdx.x;
         if (t >= trk_lo(a) && t <= trk_hi(a) && t < n_it) {
             double sd = 0.0, sn = 0.0;
-            for (int ww = 0; ww < NW; ++ww)
+            for (int ww = 0; ww < TV_NW; ++ww)
                 for (int q = 0; q < 4; ++q) { sd += sh.red[t][ww][q].x; sn += sh.red[t][ww][q].y; }
             if (!EXACT) sd *= (double)(a.rho * a.rho);     // fast sums hold (x - x2_prev)^2
             // Round 6: deepinv stops when ||x2 - x2_prev|| < tol ||x2||, i.e. sum(d) < tol^2 sum(n) over the chain's
@@ -418,10 +422,9 @@ __device__ __forceinline__ void sb_tile(const TvArgs& a, TileShared<R, NW>& sh, 
     }
 }
 
-template <bool EXACT, bool ALPHA1, int R, bool GEN, int NW, int FRONT>
-__global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
-    __shared__ TileShared<R, NW> sh;
-    constexpr bool SPLIT = NW == 8;                    // two-phase arrival (below)
+template <bool EXACT, bool ALPHA1, int R, bool GEN, int FRONT>
+__global__ void __launch_bounds__(TV_THREADS) tv_tile_kernel(const TvArgs a) {
+    __shared__ TileShared<R> sh;
     const long long step = launch_step(a);
     const bool fresh = launch_fresh(a);
     if (threadIdx.x == 0) sh.s_uncert = 0;             // (read after sb_tile's barriers)
@@ -450,36 +453,33 @@ __global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
                     const int band = t - seg * a.nbands;
                     const int nstop = __builtin_amdgcn_readfirstlane(a.redo[4 + plane / a.C]);
                     if (nstop < a.n_tv)
-                        sb_tile<EXACT, ALPHA1, R, GEN, NW, FRONT>(a, sh, plane, seg, band, nstop, false, step - 1,
-                                                           (pend & 2) != 0, [] {});
+                        sb_tile<EXACT, ALPHA1, R, GEN, FRONT>(a, sh, plane, seg, band, nstop, false, step - 1,
+                                                              (pend & 2) != 0, [] {});
                 }
                 if (!a.redo_only) grid_sync(a.redo + 1, a.arrive + 3);
             }
             if (a.redo_only) return;
         }
-        // Arrival.  The 72-row tiles (SPLIT) arrive before their u2 stores, so those drain while the last
-        // workgroup finalises (16 chains 68.3 -> 67.0 us; the 16-wave tiles measured +1-1.4 % that way,
-        // profiles/r03s_tile_two_phase_ab.txt): the counter a.arrive then holds two counts, the low 16 bits
-        // the workgroups whose rel-err sums and X side are complete (phase 1: the last one finalises the
-        // step), the high bits those whose u2 stores are complete too (phase 2: the rare early-stop recompute
-        // rewrites outputs, so it waits for them); the last workgroup takes both counts out at the end, by
-        // one atomic add.  The other tiles arrive once everything is stored (phase 1 only).
+        // Arrival.  Every workgroup arrives once, after all its stores (rel-err sums, X side, u2) are complete, by
+        // one add to a.arrive, which packs two counts: the low 16 bits the workgroups that arrived -- the one whose
+        // add returns the last count finalises the step -- and the high half the tiles whose rel-err partials leave
+        // a stop possible (sb_tile's s_uncert; 0: the finaliser takes its no-stop path).  (An arrival before the u2
+        // stores was measured and is not kept: DESIGN.md 3.2.)
+        // Without fences: every output of this kernel is an sc1 (write-through) store and every rel-err sum
+        // an agent-scope atomic; each wave waits vmcnt(0) before the barrier in front of the add, one lane per
+        // workgroup adds to the arrival counter, and the workgroup whose add returns the last count reads the sums
+        // by agent atomics (MI355X_MICROARCH.md: "8-B agent atomics both sides" with its hand-off row 1; a
+        // release + acquire pair cost 1.1 us per step here).  Nothing else this launch wrote is read by it
+        // (the rare redo reads the step's inputs, written by the previous launch).
         auto arrive = [&]() {
             if (!a.fin_inline) return;
             wait_vm0();
             __syncthreads();
             if (threadIdx.x == 0) {
-        // Without fences: every output of this kernel is an sc1 (write-through) store and every rel-err sum
-        // an agent-scope atomic; each wave waited vmcnt(0) before the barrier above, one lane per workgroup
-        // adds to the arrival counter, and the workgroup whose add returns the last count reads the sums by
-        // agent atomics (MI355X_MICROARCH.md: "8-B agent atomics both sides" with its hand-off row 1; a
-        // release + acquire pair cost 1.1 us per step here).  Nothing else this launch wrote is read by it
-        // (the rare redo reads the step's inputs, written by the previous launch).
-                // (one-phase arrival: the high half counts the tiles whose rel-err partials leave a stop possible)
-                const int unc = SPLIT ? 0 : (sh.s_uncert ? 1 : 0);
+                const int unc = sh.s_uncert ? 1 : 0;
                 const int old = __hip_atomic_fetch_add(a.arrive, 1 + (unc << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 sh.s_flag = ((old & 0xFFFF) == (int)gridDim.x - 1) ? 1 : 0;
-                sh.s_nuncert = SPLIT ? 1 : (old >> 16) + unc;
+                sh.s_nuncert = (old >> 16) + unc;
             }
             wait_vm0();
             __syncthreads();
@@ -488,20 +488,12 @@ __global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
             const int plane = item / T, t = item - plane * T;
             const int seg = GEN ? t / a.nbands : 0;
             const int band = t - seg * a.nbands;
-            if constexpr (SPLIT) sb_tile<EXACT, ALPHA1, R, GEN, NW, FRONT>(a, sh, plane, seg, band, a.n_tv, true, step, fresh, arrive);
-            else sb_tile<EXACT, ALPHA1, R, GEN, NW, FRONT>(a, sh, plane, seg, band, a.n_tv, true, step, fresh, [] {});
+            sb_tile<EXACT, ALPHA1, R, GEN, FRONT>(a, sh, plane, seg, band, a.n_tv, true, step, fresh, [] {});
         }
-        if (!SPLIT || item >= N) arrive();
+        arrive();
     }
     if (!a.fin_inline) return;
-    if (!sh.s_flag) {
-        if (!SPLIT) return;
-        // phase 2: this workgroup's u2 stores are complete
-        wait_vm0();
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_fetch_add(a.arrive, 1 << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
+    if (!sh.s_flag) return;
     // ---- step finalisation by the last workgroup to arrive (as tv_stream_kernel) ----
     const int G = a.B;
     const int ncp = a.norm_copies;
@@ -608,19 +600,8 @@ __global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
             a.redo[0] = sh.s_item ? (1 | (fresh ? 2 : 0)) : 0;
         }
     } else if (sh.s_item) {
-        // rare: redo every tile of a stopped chain with the stopped iteration count (inputs intact), once every
-        // other workgroup's stores are complete (phase 2; all of them have arrived, so each will count: bounded
-        // wait only as a guard)
-        if (SPLIT && threadIdx.x == 0) {
-            bool done = false;
-            for (int spin = 0; spin < (1 << 24) && !done; ++spin) {
-                done = (__hip_atomic_load(a.arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 16) >= (int)gridDim.x - 1;
-                if (!done) __builtin_amdgcn_s_sleep(2);
-            }
-            // the guard expired: the redo may race late first-pass stores -- record it for the host
-            // (arrive[3], read by FusedTvChains.check_handoff()) instead of going on silently
-            if (!done) __hip_atomic_store(a.arrive + 3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        // rare: redo every tile of a stopped chain with the stopped iteration count (the step's inputs are intact).
+        // Every other workgroup arrived after all its stores completed, so the redo's stores land after theirs
         wait_vm0();
         __syncthreads();
         for (int item = 0; item < P * T; ++item) {
@@ -629,7 +610,7 @@ __global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
             const int band = t - seg * a.nbands;
             const int nstop = __builtin_amdgcn_readfirstlane(sh.s_stop[plane / a.C]);
             if (nstop < a.n_tv) {
-                sb_tile<EXACT, ALPHA1, R, GEN, NW, FRONT>(a, sh, plane, seg, band, nstop, false, step, fresh, [] {});
+                sb_tile<EXACT, ALPHA1, R, GEN, FRONT>(a, sh, plane, seg, band, nstop, false, step, fresh, [] {});
                 wait_vm0();
                 __syncthreads();
             }
@@ -640,47 +621,47 @@ __global__ void __launch_bounds__(NW * WAVE) tv_tile_kernel(const TvArgs a) {
     // (the norm copies were zeroed by the exchanges that read them, or by the stores above; entries outside the
     // tracked iterations are never written)
     if (threadIdx.x == 0) {
-        // both counts out (the other workgroups' phase-2 adds may still be landing: an add, not a store); the
-        // counter is 0 once the kernel has completed
-        const int G1 = (int)gridDim.x;
-        if (SPLIT) __hip_atomic_fetch_add(a.arrive, -(G1 + ((G1 - 1) << 16)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *a.arrive = 0;
+        // both counts out by a plain store: every workgroup of the launch has made its one add
+        *a.arrive = 0;
         if (a.fresh_dev) *a.fresh_dev = 0;
         if (a.advance_step && a.d_step) *a.d_step = step - a.step_offset + 1;   // the value read at the start: no dependent load
     }
 }
 
+// The shipped instances of this unit's front, written once: the kernel of (exact, alpha1, gen, tile_r) and its slot
+// in the occupancy cache, or a null kernel.  launch_tile launches this pointer and tile_blocks_per_cu asks the runtime
+// for the occupancy of the same one, so the answer that allows the parallel redo's grid barrier always describes the
+// kernel that runs.  They are the instances select_step_kernel (api.hip) dispatches -- none spills a VGPR (round 6,
+// DESIGN.md 3.9; checked by tests/test_native_abi.py): 32-row tiles everywhere, 48-row tiles at alpha = 1 only
+// (alpha != 1 spilled 1-12 VGPRs)
+struct TileInstance {
+    void (*kernel)(TvArgs);
+    int slot;
+};
+static TileInstance tile_instance(bool exact, bool alpha1, bool gen, int tile_r) {
+    const int slot = (exact ? 8 : 0) | (alpha1 ? 4 : 0) | (gen ? 2 : 0) | (tile_r == 3 ? 1 : 0);
+#define PSGLA_TILE(E, A, RV) \
+    if (exact == E && alpha1 == A && tile_r == RV) \
+        return {gen ? &tv_tile_kernel<E, A, RV, true, PSGLA_TILE_FRONT> : &tv_tile_kernel<E, A, RV, false, PSGLA_TILE_FRONT>, slot};
+    PSGLA_TILE(true, true, 2) PSGLA_TILE(true, false, 2) PSGLA_TILE(false, true, 2) PSGLA_TILE(false, false, 2)
+    PSGLA_TILE(true, true, 3) PSGLA_TILE(false, true, 3)
+#undef PSGLA_TILE
+    return {nullptr, 0};
+}
+
 template <>
-int tile_blocks_per_cu<PSGLA_TILE_FRONT>(const TvArgs& s, bool exact, bool alpha1, bool gen) {
+int tile_blocks_per_cu<PSGLA_TILE_FRONT>(bool exact, bool alpha1, bool gen, int tile_r) {
     static int cache[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-    const int slot = (exact ? 8 : 0) | (alpha1 ? 4 : 0) | (gen ? 2 : 0) | (s.tile_r == 3 ? 1 : 0);
-#define PSGLA_TILE_OCC(E, A, NWV, RV) \
-    if (exact == E && alpha1 == A && s.tile_nw == NWV && s.tile_r == RV) \
-        return occupancy_cached(cache, slot, gen ? reinterpret_cast<const void*>(&tv_tile_kernel<E, A, RV, true, NWV, PSGLA_TILE_FRONT>) \
-                                                 : reinterpret_cast<const void*>(&tv_tile_kernel<E, A, RV, false, NWV, PSGLA_TILE_FRONT>), NWV * WAVE);
-    PSGLA_TILE_OCC(true, true, 16, 2) PSGLA_TILE_OCC(true, false, 16, 2) PSGLA_TILE_OCC(false, true, 16, 2) PSGLA_TILE_OCC(false, false, 16, 2)
-    PSGLA_TILE_OCC(true, true, 16, 3) PSGLA_TILE_OCC(false, true, 16, 3)
-#undef PSGLA_TILE_OCC
-    return 0;
+    const TileInstance ti = tile_instance(exact, alpha1, gen, tile_r);
+    return ti.kernel ? occupancy_cached(cache, ti.slot, reinterpret_cast<const void*>(ti.kernel), TV_THREADS) : 0;
 }
 
 template <>
 bool launch_tile<PSGLA_TILE_FRONT>(const TvArgs& s, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen) {
-#define PSGLA_TILE(E, A, NWV, RV) \
-    if (exact == E && alpha1 == A && s.tile_nw == NWV && s.tile_r == RV) { \
-        if (!gen) hipLaunchKernelGGL((tv_tile_kernel<E, A, RV, false, NWV, PSGLA_TILE_FRONT>), grid, dim3(NWV * WAVE), 0, st, s); \
-        else hipLaunchKernelGGL((tv_tile_kernel<E, A, RV, true, NWV, PSGLA_TILE_FRONT>), grid, dim3(NWV * WAVE), 0, st, s);      \
-        return true; \
-    }
-    // the instances select_step_kernel (api.hip) dispatches -- none spills a VGPR (round 6; checked by
-    // tests/test_native_abi.py): 32-row tiles everywhere, 48-row tiles at alpha = 1 (alpha != 1 spilled 1-12 VGPRs);
-    // no 72-row tiles (8 waves x 9 rows spilled 11-68 VGPRs at 256)
-#define PSGLA_TILES(E, A) PSGLA_TILE(E, A, 16, 2)
-    PSGLA_TILES(true, true) PSGLA_TILES(true, false) PSGLA_TILES(false, true) PSGLA_TILES(false, false)
-    PSGLA_TILE(true, true, 16, 3) PSGLA_TILE(false, true, 16, 3)
-#undef PSGLA_TILES
-#undef PSGLA_TILE
-    return false;
+    const TileInstance ti = tile_instance(exact, alpha1, gen, s.tile_r);
+    if (!ti.kernel) return false;
+    hipLaunchKernelGGL(ti.kernel, grid, dim3(TV_THREADS), 0, st, s);
+    return true;
 }
 
 }  // namespace psgla

@@ -1,5 +1,5 @@
 """Compile one translation unit with -Rpass-analysis=kernel-resource-usage and print one line per kernel:
-VGPRs, AGPRs, spills, scratch, occupancy.  Usage: python3 tools/kernel_resources.py csrc/tv_stream.hip [-Dflags]"""
+VGPRs, AGPRs, spills, scratch, LDS, occupancy.  Usage: python3 tools/kernel_resources.py csrc/tv_stream.hip [-Dflags]"""
 import os
 import re
 import subprocess
@@ -10,7 +10,8 @@ sys.path.insert(0, REPO)
 from psgla_for_posterior_sampling_amd import build as B  # noqa: E402
 
 src = sys.argv[1]
-cmd = [B.hipcc(), f"--offload-arch={B.ARCH}"] + B.FLAGS + ["-I", os.path.join(REPO, "include"), "-I", B.CSRC,
+unit = os.path.splitext(os.path.basename(src))[0]   # (the unit's own build flags: tv_tile's scheduler strategy)
+cmd = [B.hipcc(), f"--offload-arch={B.ARCH}"] + B.FLAGS + B.UNIT_FLAGS.get(unit, []) + ["-I", os.path.join(REPO, "include"), "-I", B.CSRC,
                                                            "-I", os.path.dirname(os.path.abspath(src))] + \
     sys.argv[2:] + ["-c", src, "-o", "/tmp/_kr.o", "-Rpass-analysis=kernel-resource-usage"]
 out = subprocess.run(cmd, capture_output=True, text=True)
@@ -31,5 +32,6 @@ for r in rows:
     n = subprocess.run(["c++filt"], input=r["name"], capture_output=True, text=True).stdout.strip()
     print(f"{n[:90]:90s} vgpr {r.get('VGPRs', '?'):>4s} agpr {r.get('AGPRs', '?'):>3s} "
           f"vspill {r.get('VGPRs Spill', '?'):>3s} sspill {r.get('SGPRs Spill', '?'):>4s} "
-          f"scratch {r.get('ScratchSize [bytes/lane]', '?'):>4s} occ {r.get('Occupancy [waves/SIMD]', '?')}")
+          f"scratch {r.get('ScratchSize [bytes/lane]', '?'):>4s} lds {r.get('LDS Size [bytes/block]', '?'):>6s} "
+          f"occ {r.get('Occupancy [waves/SIMD]', '?')}")
 sys.exit(out.returncode)

@@ -16,10 +16,10 @@ __device__ __forceinline__ void tdiag(long long step, int i) {
         p[((size_t)(step & 1) * 4096 + blockIdx.x) * 8 + i] = __builtin_amdgcn_s_memrealtime();
 }
 
-template <int R, int NW>
+template <int R>
 struct TileShared {'''
 PATCHES = [
-    ("\ntemplate <int R, int NW>\nstruct TileShared {", DEFS, 1),
+    ("\ntemplate <int R>\nstruct TileShared {", DEFS, 1),
     ("    // ---- 3. data term Y = (X + c1 g) + c2 Z, TV start state", "    if (track) tdiag(step, 1);\n    // ---- 3. data term Y = (X + c1 g) + c2 Z, TV start state", 1),
     ("    __syncthreads();\n    // The previous mean / sq of the core rows", "    __syncthreads();\n    if (track) tdiag(step, 2);\n    // The previous mean / sq of the core rows", 1),
     ("    if (n_it > 0) iteration(n_it - 1, std::true_type{}, std::integral_constant<int, 2>{});\n",
