@@ -172,6 +172,55 @@ int psgla_tv_step(const PsglaTvStep* d, const PsglaSchedule* s, void* stream);
 int psgla_tv_step_kernel(const PsglaTvStep* d);
 
 /* ---------------------------------------------------------------------------------
+ * psgla_tv_ula_step: ONE fused PnP-ULA Langevin step whose denoiser is the warm-started TV prox ("MYULA with a TV
+ * prior") and whose data term is the inpainting fidelity, for B chains.  Replaces one iteration of
+ *   restoration_algorithms.py:103-144 with
+ *   prior_grad = sampling_images.py:156-157  (alpha*(D(x, s1) - x)/s2, D = deepinv 0.2.1 TVDenoiser(n_it_max))
+ *   data_grad  = sampling_images.py:295      (-mask*(x - y)/sigma2)
+ * i.e. today's three launches TVDenoiser.forward (psgla_tv_prox + finaliser) and pnpula_prior_update, in one:
+ *   D  = TVprox_ths(X)            warm-started from (x2, u2); ths = s1
+ *   X' = (X + delta*((alpha*(D - X)/s2 - (X - proj(X))/lambd) + gd(X))) + brw*Z
+ * Added to ABI 12 (symbols only; PsglaTvStep is unchanged).  The embedded `tv` descriptor keeps psgla_tv_step's
+ * meaning -- geometry, ping-pong state, observation, TV constants, seed, workspace, variants -- except:
+ *   tv.alpha       the prior's alpha (a coefficient, not a relaxation);
+ *   tv.ths         s1;
+ *   tv.c1, tv.c2   unused;
+ *   tv.data_term   must be 0 (the inpainting data term is computed in the kernel from y, mask and sigma2); any
+ *                  other value is rejected;
+ *   tv.x2[0], tv.x2[1]  must be non-NULL: the prox output D is never the chain state X', so the TV primal always
+ *                  has ping-pong buffers of its own (the kernels' "alpha != 1" layout; there is no other).
+ * One call, per chain and step i:
+ *   - step i reads x[i&1], x2[i&1], u2[i&1], mean, sq;
+ *   - `fresh` gives x2 = X, u2 = 0;
+ *   - D is the result of n_tv TV iterations on input X (padding columns are fed as 0);
+ *   - Z is the "psgla noise v2" quad stream of (seed, chain0 + b, i, TAG_LANGEVIN): the stream pnpula_update uses;
+ *   - exact mode (tv.exact == 1) uses the fp32 operations of pnpula_prior_update, in its order:
+ *       gp = (alpha*(D - X))/s2;  gd = ((-m)*(X - y))/sigma2;
+ *       out = X > c_min ? X : c_min;  proj = out < c_max ? out : c_max;
+ *       gpi = (gp - (X - proj)/lambd) + gd;  X' = (X + delta*gpi) + brw*Z
+ *     (bit-identical to TVDenoiser.forward + pnpula_prior_update for one chain); fast mode fuses into fma and
+ *     multiplies by reciprocals formed on the host;
+ *   - step i writes x[(i+1)&1] = X', x2[(i+1)&1] = D and u2[(i+1)&1], the accumulators and samples of X' by
+ *     PsglaSchedule, then clears `fresh` and advances the step;
+ *   - deepinv's early stop is decided per chain, exactly as in psgla_tv_step: a stopped chain's step is recomputed
+ *     with its shorter iteration count and the same Z.
+ * launch_mask, kernel_variant (0, 1, 2), stream_wgs, stream_windows, ldw and norms_copies keep their meaning.  The
+ * parallel early-stop redo IS supported (it reads only ping-pong state and in-kernel noise, as the inpainting front's):
+ * a non-NULL `redo` and launch_mask 4 work as in psgla_tv_step, on the row stream.
+ * Kernels: the row stream (tv_stream_kernel, 1 <= n_tv <= 10, H >= 2, ldw % 4 == 0) and the band kernel + finaliser
+ * (n_tv 11-24, H < 2 or kernel_variant 1; ldw == W).  There are no tile-kernel instances yet: kernel_variant 4 is
+ * rejected, and shapes psgla_tv_step would give to tiles run on the stream (or the band kernel when n_tv > 10).
+ * ------------------------------------------------------------------------------- */
+typedef struct PsglaUlaTvStep {
+    PsglaTvStep tv;     /* geometry, state, observation, TV constants, seed, variants: as psgla_tv_step */
+    float delta, lambd, brw, c_min, c_max;   /* restoration_algorithms.py:110-115 (brw = fp32 sqrt(2 delta)) */
+    float s2;                                 /* prior: gp = (tv.alpha * (D - X)) / s2, sampling_images.py:156-157 */
+} PsglaUlaTvStep;
+int psgla_tv_ula_step(const PsglaUlaTvStep* d, const PsglaSchedule* s, void* stream);
+/* Which kernel psgla_tv_ula_step launches: 0 band kernel + finaliser, 1 row stream; -1 if rejected (never 3). */
+int psgla_tv_ula_step_kernel(const PsglaUlaTvStep* d);
+
+/* ---------------------------------------------------------------------------------
  * psgla_tv_prox: TVDenoiser.forward(y, ths) on a (B,C,H,W) tensor, deepinv 0.2.1
  * semantics: warm start from (x2_in, u2_in) unless `fresh`; early stop on the
  * relative change of the WHOLE tensor (as deepinv computes it), or of each chain

@@ -50,6 +50,14 @@ class PsglaTvStep(ctypes.Structure):
     ]
 
 
+class PsglaUlaTvStep(ctypes.Structure):
+    """The fused PnP-ULA + TV step's descriptor: psgla_tv_step's, then the ULA update's scalars (psgla_hip.h)."""
+    _fields_ = [
+        ("tv", PsglaTvStep),
+        ("delta", c_f), ("lambd", c_f), ("brw", c_f), ("c_min", c_f), ("c_max", c_f), ("s2", c_f),
+    ]
+
+
 class PsglaTvProx(ctypes.Structure):
     _fields_ = [
         ("B", c_i32), ("C", c_i32), ("H", c_i32), ("W", c_i32),
@@ -66,6 +74,8 @@ _SIGNATURES = {
     "psgla_tv_step": (c_i32, [ctypes.POINTER(PsglaTvStep), ctypes.POINTER(PsglaSchedule), c_vp]),
     "psgla_tv_prox": (c_i32, [ctypes.POINTER(PsglaTvProx), c_vp]),
     "psgla_tv_step_kernel": (c_i32, [ctypes.POINTER(PsglaTvStep)]),
+    "psgla_tv_ula_step": (c_i32, [ctypes.POINTER(PsglaUlaTvStep), ctypes.POINTER(PsglaSchedule), c_vp]),
+    "psgla_tv_ula_step_kernel": (c_i32, [ctypes.POINTER(PsglaUlaTvStep)]),
     "psgla_normal_fill": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_u64, c_i32, c_vp, c_i64, c_u32, c_vp]),
     "psgla_langevin_update": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f, c_f, c_u64, c_i32, c_vp,
                                       c_i64, c_vp]),

@@ -139,25 +139,29 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
     // of it, nothing else), then clear the pending flag; only the stream / tile kernels with a redo buffer have one
     // (with a given Y -- data_term 1 -- there is no parallel redo: launch_mask 4 is a no-op)
     if (mask == 4) {
-        if (FRONT != FRONT_INPAINT || !a.redo || (a.tile_r == 0 && !a.stream)) return 0;
+        // (FRONT_ULA: the row stream's redo, as the inpainting front's; it has no tile instances)
+        constexpr int FR = FRONT == FRONT_ULA ? FRONT_ULA : FRONT_INPAINT;
+        if ((FRONT != FRONT_INPAINT && FRONT != FRONT_ULA) || !a.redo || (a.tile_r == 0 && !a.stream)) return 0;
         TvArgs s = a;
         s.fin_inline = 0;
         s.redo_only = 1;
-        int rc;
+        int rc = 0;
         if (a.tile_r > 0) {
-            const int grid = P * s.nbands * s.st_nsegs;
-            const bool gen = !(s.ldw == s.W && s.st_nsegs == 1);
-            s.par_redo = grid_resident(grid, tile_blocks_per_cu<FRONT_INPAINT>(EXACT, ALPHA1, gen, s.tile_r)) ? 1 : 0;
-            if (!s.par_redo) return 0;   // (the tile kernel's finaliser recomputed stopped chains itself)
-            if (!launch_tile<FRONT_INPAINT>(s, dim3(grid), st, EXACT, ALPHA1, gen))
-                return fail(0, "psgla_tv_step: internal error: no tile kernel of this shape");
-            rc = launch_check("tv_tile_kernel(redo)");
+            if constexpr (FRONT != FRONT_ULA) {
+                const int grid = P * s.nbands * s.st_nsegs;
+                const bool gen = !(s.ldw == s.W && s.st_nsegs == 1);
+                s.par_redo = grid_resident(grid, tile_blocks_per_cu<FRONT_INPAINT>(EXACT, ALPHA1, gen, s.tile_r)) ? 1 : 0;
+                if (!s.par_redo) return 0;   // (the tile kernel's finaliser recomputed stopped chains itself)
+                if (!launch_tile<FRONT_INPAINT>(s, dim3(grid), st, EXACT, ALPHA1, gen))
+                    return fail(0, "psgla_tv_step: internal error: no tile kernel of this shape");
+                rc = launch_check("tv_tile_kernel(redo)");
+            }
         } else {
             const int grid = s.split_wgs > 0 ? s.split_wgs : s.st_nvp;
-            s.par_redo = grid_resident(grid, stream_blocks_per_cu<FRONT_INPAINT>(EXACT, ALPHA1, !(s.ldw == s.W && s.st_nsegs == 1),
-                                                                                 s.st_half != 0)) ? 1 : 0;
+            s.par_redo = grid_resident(grid, stream_blocks_per_cu<FR>(EXACT, ALPHA1, !(s.ldw == s.W && s.st_nsegs == 1),
+                                                                      s.st_half != 0)) ? 1 : 0;
             if (!s.par_redo) return 0;
-            launch_stream<FRONT_INPAINT>(s, dim3(grid), st, EXACT, ALPHA1, !(s.ldw == s.W && s.st_nsegs == 1), s.st_half != 0);
+            launch_stream<FR>(s, dim3(grid), st, EXACT, ALPHA1, !(s.ldw == s.W && s.st_nsegs == 1), s.st_half != 0);
             rc = launch_check("tv_stream_kernel(redo)");
         }
         if (rc) return rc;
@@ -168,7 +172,8 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
     // instances this launch takes (never referenced for the bare prox, which has none)
     constexpr int FS = FRONT == FRONT_GIVEN ? FRONT_INPAINT : FRONT;
     if (mask & 1) {
-        if (FRONT != FRONT_GIVEN && a.tile_r > 0) {
+        if (FRONT != FRONT_GIVEN && FRONT != FRONT_ULA && a.tile_r > 0) {
+          if constexpr (FRONT != FRONT_ULA) {
             TvArgs s = a;
             s.fin_inline = (mask & 2) ? 1 : 0;
             const int grid = P * s.nbands * s.st_nsegs;                   // tile_kernel: one workgroup per tile
@@ -185,6 +190,7 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
             s.par_redo = (s.redo && grid_resident(grid, tile_blocks_per_cu<FS>(EXACT, ALPHA1, gen, s.tile_r))) ? 1 : 0;
             if (launch_tile<FS>(s, dim3(grid), st, EXACT, ALPHA1, gen)) return launch_check("tv_tile_kernel");
             return fail(0, "psgla_tv_step: internal error: no tile kernel of this shape");
+          }
         }
         if (FRONT != FRONT_GIVEN && a.stream) {
             TvArgs s = a;
@@ -231,7 +237,9 @@ static bool tv_fast_constants(const TvArgs& a) {
     return a.tau == TV_TAU && a.opt == TV_OPT && a.sig_tv == TV_SIG && a.rho == TV_RHO && a.inv_opt == TV_INV_OPT;
 }
 
-static int select_step_kernel(const PsglaTvStep* d, TvArgs& a) {
+// tiles = false (psgla_tv_ula_step: no ULA tile instances yet): shapes the tile kernel would take go to the row stream,
+// or to the band kernel when n_tv > 10
+static int select_step_kernel(const PsglaTvStep* d, TvArgs& a, bool tiles = true) {
     a.halo = d->n_tv;
     tv_tiling(a);
     const bool streamable = (a.ldw % 4 == 0) && d->n_tv >= 1 && d->n_tv <= SP_MAXST && d->H >= 2 &&
@@ -247,7 +255,7 @@ static int select_step_kernel(const PsglaTvStep* d, TvArgs& a) {
     // on the CUs, see below (a row stream would be mostly pipeline fill: strong scaling's 64/N chains per GPU)
     a.tile_r = 0;
     int tile_segs = 0, tile_sw = 0;
-    if (d->kernel_variant == 4 || d->kernel_variant == 0) {
+    if (tiles && (d->kernel_variant == 4 || d->kernel_variant == 0)) {
         const int P = d->B * d->C;
         int bh = 0, nb = 0;
         // column segments as the stream kernel's (one when ldw == W <= 256)
@@ -324,13 +332,9 @@ static int select_step_kernel(const PsglaTvStep* d, TvArgs& a) {
     return 0;
 }
 
-extern "C" {
-
-int psgla_abi_version(void) { return PSGLA_HIP_ABI_VERSION; }
-const char* psgla_last_error(void) { return g_err; }
-
-int psgla_tv_step(const PsglaTvStep* d, const PsglaSchedule* s, void* stream) {
-    if (!d || !s) return fail(0, "psgla_tv_step: null descriptor");
+// psgla_tv_step's checks of a descriptor and its argument block (everything but the kernel selection); shared with
+// psgla_tv_ula_step, whose embedded descriptor has the same geometry, state, observation, TV constants and schedule
+static int tv_step_args(const PsglaTvStep* d, const PsglaSchedule* s, TvArgs& a) {
     int rc = check_tv_common(d->B, d->C, d->H, d->W, d->n_tv);
     if (rc) return rc;
     const bool alpha1 = d->x2[0] == nullptr;
@@ -342,7 +346,6 @@ int psgla_tv_step(const PsglaTvStep* d, const PsglaSchedule* s, void* stream) {
     if (!alpha1 && !d->x2[1]) return fail(0, "psgla_tv_step: x2[1] missing");
     if (s->n_inter_mmse >= 0 && (!d->mean[0] || !d->mean[1] || !d->sq[0] || !d->sq[1] || !s->acc_coef))
         return fail(0, "psgla_tv_step: accumulators missing");
-    TvArgs a;
     memset(&a, 0, sizeof(a));
     a.B = d->B; a.C = d->C; a.H = d->H; a.W = d->W;
     a.ldw = d->ldw > 0 ? d->ldw : d->W;
@@ -377,6 +380,32 @@ int psgla_tv_step(const PsglaTvStep* d, const PsglaSchedule* s, void* stream) {
         a.mask = nullptr; a.m_cs = 0;
     }
     if (d->launch_mask < 0 || d->launch_mask > 4) return fail(0, "psgla_tv_step: launch_mask must be 0 .. 4");
+    return 0;
+}
+
+// What psgla_tv_ula_step requires of its embedded descriptor beyond psgla_tv_step's checks (0: fine; else g_err set)
+static int ula_check(const PsglaTvStep* t) {
+    if (t->data_term != 0)
+        return fail(0, "psgla_tv_ula_step: tv.data_term must be 0 (the inpainting data term is computed in the kernel)");
+    if (!t->x2[0] || !t->x2[1])
+        return fail(0, "psgla_tv_ula_step: tv.x2[0] and tv.x2[1] are required (the prox output is never the chain state)");
+    if (t->kernel_variant == 4)
+        return fail(0, "psgla_tv_ula_step: kernel_variant 4: the tile kernel has no ULA instances (use 0, 1 or 2)");
+    return 0;
+}
+
+extern "C" {
+
+int psgla_abi_version(void) { return PSGLA_HIP_ABI_VERSION; }
+const char* psgla_last_error(void) { return g_err; }
+
+int psgla_tv_step(const PsglaTvStep* d, const PsglaSchedule* s, void* stream) {
+    if (!d || !s) return fail(0, "psgla_tv_step: null descriptor");
+    TvArgs a;
+    int rc = tv_step_args(d, s, a);
+    if (rc) return rc;
+    const bool alpha1 = d->x2[0] == nullptr;
+    const bool given = d->data_term == 1;
     if (select_step_kernel(d, a) < 0) return g_sel_err == g_err ? (int)hipErrorInvalidValue : fail(0, g_sel_err);
     hipStream_t st = (hipStream_t)stream;
     const int m = d->launch_mask;
@@ -404,6 +433,41 @@ int psgla_tv_step_kernel(const PsglaTvStep* d) {
     a.B = d->B; a.C = d->C; a.H = d->H; a.W = d->W;
     a.ldw = d->ldw > 0 ? d->ldw : d->W;
     const int k = select_step_kernel(d, a);
+    if (k < 0 && g_sel_err != g_err) fail(0, g_sel_err);
+    return k;
+}
+
+int psgla_tv_ula_step(const PsglaUlaTvStep* d, const PsglaSchedule* s, void* stream) {
+    if (!d || !s) return fail(0, "psgla_tv_ula_step: null descriptor");
+    const PsglaTvStep* t = &d->tv;
+    int rc = check_tv_common(t->B, t->C, t->H, t->W, t->n_tv);
+    if (rc) return rc;
+    rc = ula_check(t);
+    if (rc) return rc;
+    TvArgs a;
+    rc = tv_step_args(t, s, a);
+    if (rc) return rc;
+    if (!(d->lambd != 0.f) || !(d->s2 != 0.f)) return fail(0, "psgla_tv_ula_step: lambd and s2 must be non-zero");
+    a.u_delta = d->delta; a.u_lambd = d->lambd; a.u_brw = d->brw; a.u_cmin = d->c_min; a.u_cmax = d->c_max;
+    a.u_s2 = d->s2;
+    a.u_inv_lambd = (float)(1.0 / (double)d->lambd);
+    a.u_ca = (float)((double)d->delta * (double)t->alpha / (double)d->s2);
+    if (select_step_kernel(t, a, false) < 0) return g_sel_err == g_err ? (int)hipErrorInvalidValue : fail(0, g_sel_err);
+    hipStream_t st = (hipStream_t)stream;
+    if (t->exact || !tv_fast_constants(a)) return launch_tv<true, FRONT_ULA, false>(a, st, t->launch_mask);
+    return launch_tv<false, FRONT_ULA, false>(a, st, t->launch_mask);
+}
+
+int psgla_tv_ula_step_kernel(const PsglaUlaTvStep* d) {
+    if (!d) { fail(0, "psgla_tv_ula_step_kernel: null descriptor"); return -1; }
+    const PsglaTvStep* t = &d->tv;
+    if (check_tv_common(t->B, t->C, t->H, t->W, t->n_tv)) return -1;
+    if (ula_check(t)) return -1;
+    TvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = t->B; a.C = t->C; a.H = t->H; a.W = t->W;
+    a.ldw = t->ldw > 0 ? t->ldw : t->W;
+    const int k = select_step_kernel(t, a, false);
     if (k < 0 && g_sel_err != g_err) fail(0, g_sel_err);
     return k;
 }

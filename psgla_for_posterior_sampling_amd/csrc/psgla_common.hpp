@@ -92,8 +92,10 @@ constexpr float TV_RHO = 0x1.fd70a4p+0f;       // fp32(1.99)
 
 // FRONT_INPAINT: the fused step with the inpainting data term; FRONT_GIVEN: the stand-alone prox of a given tensor
 // (psgla_tv_prox: no ping-pong, no schedule); FRONT_STEP_GIVEN: the fused step whose Y an earlier launch produced
-// (PsglaTvStep.data_term 1: FRONT_INPAINT's whole epilogue, only the front differs -- Y is loaded through yobs)
-enum Front { FRONT_INPAINT = 0, FRONT_GIVEN = 1, FRONT_STEP_GIVEN = 2 };
+// (PsglaTvStep.data_term 1: FRONT_INPAINT's whole epilogue, only the front differs -- Y is loaded through yobs);
+// FRONT_ULA: the fused PnP-ULA + TV step (psgla_tv_ula_step): the TV input is X itself, the epilogue applies the ULA
+// update (ula_update, below) where PSGLA applies the relaxation; always the x2-separate layout (ALPHA1 = false)
+enum Front { FRONT_INPAINT = 0, FRONT_GIVEN = 1, FRONT_STEP_GIVEN = 2, FRONT_ULA = 3 };
 
 struct TvArgs {
     int B, C, H, W;
@@ -148,7 +150,31 @@ struct TvArgs {
     int* redo;                      // stream / tile kernel: parallel early-stop redo state (PsglaTvStep.redo) or null
     int par_redo;                   // 1: the redo runs in parallel in the next launch (grid resident at once)
     int redo_only;                  // 1: settle a pending redo only (launch_mask 4)
+    // FRONT_ULA (appended: the other fronts' argument offsets are unchanged): PsglaUlaTvStep's scalars; alpha above is
+    // the prior's coefficient.  Fast kernels: u_inv_lambd = 1/lambd, u_ca = delta*alpha/s2, formed in double on the host
+    float u_delta, u_lambd, u_brw, u_cmin, u_cmax, u_s2;
+    float u_inv_lambd, u_ca;
 };
+
+// The PnP-ULA update of one element from the prox output D (restoration_algorithms.py:104-115 with the DenoiserPrior
+// of sampling_images.py:156-157 and the inpainting data term of :295).  EXACT: the fp32 operations of
+// pnpula_prior_update_kernel (elementwise.hip) in its order -- bit-identical to prox + that kernel; fast: fmas and
+// host-formed reciprocals, P = fma(delta, gd - (X - proj)/lambd, X) + brw Z, X' = fma(delta alpha / s2, D - X, P).
+template <bool EXACT>
+__device__ __forceinline__ float ula_update(const TvArgs& a, float X, float D, float yo, float mk, float Z) {
+    const float out = (X > a.u_cmin) ? X : a.u_cmin;
+    const float proj = (out < a.u_cmax) ? out : a.u_cmax;
+    if (EXACT) {
+        const float gp = (a.alpha * (D - X)) / a.u_s2;
+        const float gd = (-mk * (X - yo)) / a.sigma2;
+        const float gpi = (gp - (X - proj) / a.u_lambd) + gd;
+        return (X + a.u_delta * gpi) + a.u_brw * Z;
+    }
+    const float gd = (mk * (yo - X)) * a.inv_sigma2;
+    const float t = __builtin_fmaf(proj - X, a.u_inv_lambd, gd);
+    const float P = __builtin_fmaf(a.u_brw, Z, __builtin_fmaf(a.u_delta, t, X));
+    return __builtin_fmaf(a.u_ca, D - X, P);
+}
 
 // The launch's step index and TV restart flag, wave-uniform by construction (readfirstlane: code that stores to
 // global memory before using them must not make the compiler treat them as per-lane values)
@@ -373,7 +399,8 @@ __device__ __forceinline__ StepInfo step_info(const TvArgs& a, long long step, c
 // kernel launchers (one translation unit each)
 template <bool EXACT, int FRONT, bool ALPHA1> void launch_band_main(const TvArgs& a, dim3 grid, hipStream_t st);
 template <bool EXACT, int FRONT, bool ALPHA1> void launch_band_finalise(const TvArgs& a, dim3 grid, hipStream_t st);
-// (stream / tile: FRONT_INPAINT or FRONT_STEP_GIVEN, each front's instances in a translation unit of its own)
+// (stream / tile: FRONT_INPAINT or FRONT_STEP_GIVEN, each front's instances in a translation unit of its own;
+// FRONT_ULA: stream instances only, tv_stream_ula.hip)
 template <int FRONT> void launch_stream(const TvArgs& a, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen, bool half);
 template <int FRONT> bool launch_tile(const TvArgs& a, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen);
 // workgroups of the instance launch_stream / launch_tile would run that one CU holds at once (the runtime's occupancy

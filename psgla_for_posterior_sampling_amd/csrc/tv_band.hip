@@ -113,8 +113,11 @@ __device__ __forceinline__ void band_tile(const TvArgs& a, int plane, int tile, 
                         for (int k = 0; k < CPL; ++k) xs[k] = colok[k] ? x2in[base + k] : 0.f;
                     }
                 }
-            } else if (FRONT == FRONT_STEP_GIVEN) {  // the step's Y is given (FRONT_GIVEN's load); x2 start as FRONT_INPAINT
-                const float* yb = a.yobs + (size_t)b * a.y_cs + (size_t)c * HW + (size_t)gi[r] * W + gj0;
+            } else if (FRONT == FRONT_STEP_GIVEN || FRONT == FRONT_ULA) {
+                // the step's Y is given (FRONT_GIVEN's load); x2 start as FRONT_INPAINT.  FRONT_ULA: the prox input is
+                // X itself (no noise, no data term here: the update is applied where the core is stored)
+                const float* yb = FRONT == FRONT_ULA ? a.x[par_in] + base
+                                                     : a.yobs + (size_t)b * a.y_cs + (size_t)c * HW + (size_t)gi[r] * W + gj0;
                 const float* xsin = (fresh || ALPHA1) ? a.x[par_in] : a.x2[par_in];
                 if (vec) {
                     const float4 v = ld4(yb);
@@ -279,8 +282,34 @@ __device__ __forceinline__ void band_tile(const TvArgs& a, int plane, int tile, 
         const size_t base = plane_off + (size_t)gi[r] * W + gj0;
         float Xo[CPL];
         const float4 yrow = *reinterpret_cast<const float4*>(&sh.ylds[w * R + r][CPL * lane]);
+        if (FRONT == FRONT_ULA) {
+            // PnP-ULA: X' from X (the prox input, still in ylds), the prox output, the observation, the mask and the
+            // row's noise quad (the stream pnpula_update uses)
+            float yo[CPL] = {0.f, 0.f, 0.f, 0.f}, mk[CPL] = {0.f, 0.f, 0.f, 0.f}, Z[CPL];
+            normal_quad(a.seed, (uint32_t)(a.chain0 + b), (uint32_t)step, TAG_LANGEVIN,
+                        noise_quad((size_t)c * H + gi[r], gj0, W), Z);
+            if (gj0 < W) {
+                const float* yb = a.yobs + (size_t)b * a.y_cs + (size_t)c * HW + (size_t)gi[r] * W + gj0;
+                const uint8_t* mb = a.mask + (size_t)b * a.m_cs + (size_t)gi[r] * W + gj0;
+                if (vec) {
+                    const float4 yy = ld4(yb);
+                    const uchar4 mm = *reinterpret_cast<const uchar4*>(mb);
+                    yo[0] = yy.x; yo[1] = yy.y; yo[2] = yy.z; yo[3] = yy.w;
+                    mk[0] = (float)mm.x; mk[1] = (float)mm.y; mk[2] = (float)mm.z; mk[3] = (float)mm.w;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < CPL; ++k) {
+                        yo[k] = colok[k] ? yb[k] : 0.f;
+                        mk[k] = colok[k] ? (float)mb[k] : 0.f;
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) Xo[k] = ula_update<EXACT>(a, f4get(yrow, k), x2[r][k], yo[k], mk[k], Z[k]);
+        }
 #pragma unroll
         for (int k = 0; k < CPL; ++k) {
+            if (FRONT == FRONT_ULA) break;
             // X = (1 - alpha) Y + alpha D(Y)  (restoration_algorithms.py:238); alpha == 1 gives D(Y) exactly
             if (STEP && !ALPHA1)
                 Xo[k] = (1.0f - a.alpha) * f4get(yrow, k) + a.alpha * x2[r][k];
@@ -417,6 +446,7 @@ PSGLA_BAND(true, FRONT_INPAINT, true) PSGLA_BAND(true, FRONT_INPAINT, false) PSG
 PSGLA_BAND(false, FRONT_INPAINT, true) PSGLA_BAND(false, FRONT_INPAINT, false) PSGLA_BAND(false, FRONT_GIVEN, true)
 PSGLA_BAND(true, FRONT_STEP_GIVEN, true) PSGLA_BAND(true, FRONT_STEP_GIVEN, false)
 PSGLA_BAND(false, FRONT_STEP_GIVEN, true) PSGLA_BAND(false, FRONT_STEP_GIVEN, false)
+PSGLA_BAND(true, FRONT_ULA, false) PSGLA_BAND(false, FRONT_ULA, false)
 #undef PSGLA_BAND
 
 }  // namespace psgla

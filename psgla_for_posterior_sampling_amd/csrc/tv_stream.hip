@@ -3,7 +3,8 @@
 #include "psgla_common.hpp"
 
 // The front this translation unit instantiates the kernel for: FRONT_INPAINT here, FRONT_STEP_GIVEN through
-// tv_stream_given.hip (which defines the macro and includes this file), so the two instance sets build in parallel.
+// tv_stream_given.hip and FRONT_ULA through tv_stream_ula.hip (which define the macro and include this file), so the
+// instance sets build in parallel.
 #ifndef PSGLA_STREAM_FRONT
 #define PSGLA_STREAM_FRONT FRONT_INPAINT
 #endif
@@ -61,6 +62,11 @@ struct StreamSharedT {
     __device__ __forceinline__ float4* stUa(int fw, int q) { return A1 ? &fsx[fw][((q >> 2) % 3)][1][0] : &fsx[fw][(q >> 2) & 1][2][0]; }
     __device__ __forceinline__ float4* stUb(int fw, int q) { return A1 ? &fsx[fw][((q >> 2) % 3)][2][0] : &fsx[fw][(q >> 2) & 1][3][0]; }
     __device__ __forceinline__ float4* stX2(int fw, int q) { return &fsx[fw][(q >> 2) & 1][A1 ? 0 : 4][0]; }
+    // FRONT_ULA (!A1 only; no new LDS).  The front stages neither the observation nor the mask -- the back DMAs its
+    // own rows of both, next to mean / sq -- so the front's y part of fsx is free: it is the 8-row noise ring (row r
+    // in its front wave's part, slot (r / 4) % 2), and the back's staging is fsy (y: [back wave][slot]) and fmk (mask).
+    __device__ __forceinline__ float4* ulaZ(int r) { return &fsx[r & 3][(r >> 2) & 1][1][0]; }
+    __device__ __forceinline__ float4* ulaY(int bw, int bi) { return &fsy[2 * bw + bi][0][0]; }
 };
 
 
@@ -514,6 +520,8 @@ __device__ __forceinline__ void stage_loop(const TvArgs& a, StreamSharedT<A1>& s
 template <bool EXACT, bool ALPHA1, bool GEN, bool HALF, int FRONT>
 __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA1>& sh, const RowMap& rm, const int n,
                                             const bool track, const long long step, const bool fresh) {
+    constexpr bool ULA = FRONT == FRONT_ULA;
+    static_assert(!ULA || !ALPHA1, "the ULA step keeps the TV primal in buffers of its own");
     const int lane = threadIdx.x & (WAVE - 1);
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform (scalar branches)
     const int H = a.H, W = a.W, C = a.C;
@@ -563,8 +571,17 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
         RowCursor rc_cur, rc_dma;
         cursor_init<GEN, HALF>(a, rm, rc_cur, min(fw, Q - 1));
         cursor_init<GEN, HALF>(a, rm, rc_dma, min(fw, Q - 1));
-        // part `part` of the loads of stream row q: 0 = X, 1 = y (FRONT_STEP_GIVEN: Y), 2 = u2 (two halves),
-        // 3 = mask (+ x2; FRONT_STEP_GIVEN: x2 only, nothing at alpha = 1)
+        // FRONT_ULA: the noise is the update's, consumed by the back 3 n + 1 steps after the front is done with a
+        // row.  The wave generates the quad of the row LAG = 4 floor(3 n / 4) behind the one it is loading (its own
+        // row still: LAG % 4 == 0) and writes it to the 8-row noise ring (StreamSharedT::ulaZ) in phase 3, step
+        // r + LAG + 3; the back reads it at step r + 4 + 3 n > r + LAG + 3, and the slot's next row r + 8 is written at
+        // step r + LAG + 11 > r + 4 + 3 n (3 n - LAG <= 3): a step barrier lies between each pair.  The loop runs the
+        // lag past the last row (rows q >= Q load nothing).
+        const int LAG = ULA ? ((3 * n) >> 2) << 2 : 0;
+        RowCursor rc_z;                                     // the noise row q - LAG (FRONT_ULA)
+        if (ULA) cursor_init<GEN, HALF>(a, rm, rc_z, min(fw, Q - 1));
+        // part `part` of the loads of stream row q: 0 = X, 1 = y (FRONT_STEP_GIVEN: Y; FRONT_ULA: nothing), 2 = u2
+        // (two halves), 3 = mask (+ x2; FRONT_STEP_GIVEN / FRONT_ULA: x2 only, nothing at alpha = 1)
         auto front_issue = [&](int part, int q, const RowCursor& rc) {
             const int rr = min(rc.r, H - 1);
             const int bi = (q >> 2) & 1;
@@ -576,7 +593,7 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
             if (part == 0) {
                 glds16(xin + base, sh.stX(fw, q));
             } else if (part == 1) {
-                glds16(a.yobs + rc.g.ybase + roff, sh.stY(fw, q));
+                if (!ULA) glds16(a.yobs + rc.g.ybase + roff, sh.stY(fw, q));
             } else if (part == 2) {
                 glds16(u2in + 2 * base, sh.stUa(fw, q));
                 glds16(u2in + 2 * base + 4, sh.stUb(fw, q));
@@ -595,10 +612,24 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
         // phase (one step barrier after each), so no step decides its phase at run time.
         int t = 0;
         for (; t < fw && t < nsteps; ++t) step_barrier();
-        for (int q = fw; q < Q; q += 4) {
+        const int Qf = ULA ? max(Q, Qb + LAG) : Q;
+        for (int q = fw; q < Qf; q += 4) {
+            const bool ld = !ULA || q < Q;                  // the row exists (FRONT_ULA: else only the lagged noise)
             // ---- phase 0: Philox of row q; DMA part 0 of row q + 4
-            front_issue(0, q + 4, rc_dma);
-            {
+            if (ld) front_issue(0, q + 4, rc_dma);
+            if (ULA) {
+                // the lagged row's quad (its own segment's lanes and chain)
+                const RowGeo& g = rc_z.g;
+                const int gjz = GEN ? g.f0 + CPL * lc : gj0;
+                uint32_t c0 = noise_quad(g.rbase + (size_t)rc_z.r, gjz, W), c1 = (uint32_t)step,
+                         c2 = TAG_LANGEVIN, c3 = (uint32_t)(a.seed >> 32);
+                philox4x32_10(c0, c1, c2, c3, (uint32_t)a.seed, (uint32_t)(a.chain0 + g.bb));
+                ph0 = c0; ph1 = c1; ph2 = c2; ph3 = c3;
+                if (GEN) {
+                    gjf = rc_cur.g.f0 + CPL * lc;
+                    okf = rc_cur.g.on && gjf < W;
+                }
+            } else {
                 const RowGeo& g = rc_cur.g;
                 if (GEN) {                                  // this row's segment's lanes
                     gjf = g.f0 + CPL * lc;
@@ -615,20 +646,27 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
             }
             step_barrier();
             // ---- phase 1: Box-Muller pair 1; DMA part 1
-            front_issue(1, q + 4, rc_dma);
-            if (FRONT == FRONT_INPAINT) box_muller(ph0, ph1, zn0, zn1);
+            if (ld) front_issue(1, q + 4, rc_dma);
+            if (FRONT == FRONT_INPAINT || ULA) box_muller(ph0, ph1, zn0, zn1);
             step_barrier();
             // ---- phase 2: Box-Muller pair 2; DMA part 2
-            front_issue(2, q + 4, rc_dma);
-            if (FRONT == FRONT_INPAINT) box_muller(ph2, ph3, zn2, zn3);
+            if (ld) front_issue(2, q + 4, rc_dma);
+            if (FRONT == FRONT_INPAINT || ULA) box_muller(ph2, ph3, zn2, zn3);
             step_barrier();
             // ---- phase 3: data term of row q -> ring 0 / Y ring; DMA part 3 of row q + 4
-            {
+            if (ULA) {
+                // the lagged row's noise quad -> the noise ring (padding lanes hold values no image column reads)
+                const int rz = q - LAG;
+                if (rz >= 0 && rz < Qb) sh.ulaZ(rz)[lane] = make_float4(zn0, zn1, zn2, zn3);
+                if (rz >= 0 && rz + 4 < Q) cursor_advance<GEN, HALF>(a, rm, rc_z, 4);
+            }
+            if (ld) {
                 // row q's loads landed; parts 0-2 of row q + 4 (X, y, two halves of u2: four DMAs, issued after
                 // every part of row q) may fly.  The count does not depend on part 3, so it holds for
                 // FRONT_STEP_GIVEN too, whose part 3 is one DMA (x2) or none (alpha = 1); the front waves issue
-                // no other vector-memory operation, and the redo pass runs this same code.
-                wait_vm<4>();
+                // no other vector-memory operation, and the redo pass runs this same code.  FRONT_ULA has no y part:
+                // three DMAs (X, two halves of u2) may fly.
+                wait_vm<ULA ? 3 : 4>();
                 const int bi = (q >> 2) & 1;
                 const float4 fX = sh.stX(fw, q)[lane];
                 const float4 fYo = sh.stY(fw, q)[lane];
@@ -641,7 +679,9 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
                 float Yv[CPL];
 #pragma unroll
                 for (int k = 0; k < CPL; ++k) {
-                    if (FRONT != FRONT_INPAINT) {
+                    if (ULA) {
+                        Yv[k] = okf ? X[k] : 0.f;           // the prox input is X (padding columns: 0, as below)
+                    } else if (FRONT != FRONT_INPAINT) {
                         Yv[k] = okf ? yo[k] : 0.f;          // Y given (padding columns: 0, as below)
                     } else if (EXACT) {
                         const float g = (-mk[k] * (X[k] - yo[k])) / a.sigma2;
@@ -702,24 +742,65 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
         RowCursor rc_cur, rc_dma;
         cursor_init<GEN, HALF>(a, rm, rc_cur, min(bw, Q - 1));
         cursor_init<GEN, HALF>(a, rm, rc_dma, min(bw, Q - 1));
+        // FRONT_ULA: the row's observation and mask too (the update is applied here), row and column clamped into
+        // the plane as the front's
         auto back_issue = [&](int q, const RowCursor& rc) {
-            if (need_prev) {
+            if (need_prev || ULA) {
                 const int rr = min(rc.r, H - 1);
                 const int bi = (q >> 1) & 1;
                 const int gjr = GEN ? min(rc.g.f0 + CPL * lc, L - CPL) : gjc;
                 const size_t base = rc.g.pbase + (size_t)rr * L + gjr;
-                glds16(mean_in + base, &sh.bst[bw][bi][0][0]);
-                glds16(sq_in + base, &sh.bst[bw][bi][1][0]);
+                if (ULA) {
+                    const size_t roff = (size_t)rr * L + gjr;
+                    glds16(a.yobs + rc.g.ybase + roff, sh.ulaY(bw, bi));
+                    glds4(a.mask + rc.g.mbase + roff, &sh.fmk[bw][bi][0]);
+                }
+                if (need_prev) {
+                    glds16(mean_in + base, &sh.bst[bw][bi][0][0]);
+                    glds16(sq_in + base, &sh.bst[bw][bi][1][0]);
+                }
             }
         };
+        // DMAs of one back_issue (the waits below count them; without FRONT_ULA they wait only when need_prev)
+        const int nd = ULA ? (need_prev ? 4 : 2) : 2;
         // vector-memory stores per core row (all lanes of a wave store together; lane 0 is core)
         const int nst = 3 + (ALPHA1 ? 0 : 1) + ((si.acc && (si.blockend || si.liveout)) ? 2 : 0) + (si.sample ? 1 : 0);
         // a row's stores are spread over the wave's two steps: state + accumulators, then the rest
         bool hold = false, hcore = core;
         size_t h_base = 0;                  // per-lane element index
         float4 hM = zero4, hQ = zero4, hX = zero4;
+        // FRONT_ULA: the update itself waits for the wave's second step too -- the first only reads the row's LDS
+        // (ring n, Y ring, noise ring, staging) and stores x2 / u2, which need no arithmetic; the inputs are held
+        float4 uD = zero4, uX = zero4, uZ = zero4, uY = zero4, uM = zero4, uQ = zero4;
+        uint32_t uMk = 0u;
         auto flush_held = [&]() {
             if (!(GEN ? hcore : core)) return;
+            if constexpr (ULA) {
+                hX.x = ula_update<EXACT>(a, uX.x, uD.x, uY.x, (float)(uMk & 0xFFu), uZ.x);
+                hX.y = ula_update<EXACT>(a, uX.y, uD.y, uY.y, (float)((uMk >> 8) & 0xFFu), uZ.y);
+                hX.z = ula_update<EXACT>(a, uX.z, uD.z, uY.z, (float)((uMk >> 16) & 0xFFu), uZ.z);
+                hX.w = ula_update<EXACT>(a, uX.w, uD.w, uY.w, (float)(uMk >> 24), uZ.w);
+                st_nt(a.x[par_out] + h_base, hX);
+                if (si.acc) {
+                    // the block accumulators of X' (the operations of the other fronts' first step)
+                    const float xs[CPL] = {hX.x, hX.y, hX.z, hX.w};
+                    const float ms[CPL] = {uM.x, uM.y, uM.z, uM.w};
+                    const float qs[CPL] = {uQ.x, uQ.y, uQ.z, uQ.w};
+                    float m[CPL], qq[CPL];
+#pragma unroll
+                    for (int kk = 0; kk < CPL; ++kk) {
+                        if (si.first) {
+                            m[kk] = si.cb * xs[kk];
+                            qq[kk] = si.cb * (xs[kk] * xs[kk]);
+                        } else {
+                            m[kk] = si.ca * ms[kk] + si.cb * xs[kk];
+                            qq[kk] = si.ca * qs[kk] + si.cb * (xs[kk] * xs[kk]);
+                        }
+                    }
+                    hM = make_float4(m[0], m[1], m[2], m[3]);
+                    hQ = make_float4(qq[0], qq[1], qq[2], qq[3]);
+                }
+            }
             if (si.acc) {
                 if (si.blockend) {
                     st_nt(a.blocks + (size_t)si.blk * BE + h_base, hM);
@@ -736,7 +817,7 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
         back_issue(bw, rc_dma);
         if (bw + 2 < Q) cursor_advance<GEN, HALF>(a, rm, rc_dma, 2);
         back_issue(bw + 2, rc_dma);
-        int c1 = 2, c2 = 0;
+        int c1 = nd, c2 = 0;
         // ======================= BACK =======================
         // Row q (q % 2 == bw) leaves the pipeline at step q + 4 + 3n (stage n wrote ring n row q in the step
         // before); its accumulator / sample stores go out in the wave's next step.  Unrolled by those two
@@ -753,7 +834,22 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
                 const float4 UA = sh.ua[rn][sl][lane];
                 const float4 UB = sh.ub[rn][sl][lane];
                 float4 Xo = X2;
-                if (!ALPHA1) {
+                if (ULA) {
+                    // the update's inputs: X (the Y ring's row: the prox input), D = X2, the row's staged observation,
+                    // mask and accumulators (DMA issued just before the previous row's stores) and the front's noise
+                    // quad; X' itself is formed in the wave's next step (flush_held)
+                    wait_vm_n(c1);
+                    const int bi = (q >> 1) & 1;
+                    uD = X2;
+                    uX = sh.y[q & (SP_YRING - 1)][lane];
+                    uZ = sh.ulaZ(q)[lane];
+                    uY = sh.ulaY(bw, bi)[lane];
+                    uMk = sh.fmk[bw][bi][lane];
+                    if (need_prev) {
+                        uM = sh.bst[bw][bi][0][lane];
+                        uQ = sh.bst[bw][bi][1][lane];
+                    }
+                } else if (!ALPHA1) {
                     const float4 YY = sh.y[q & (SP_YRING - 1)][lane];
                     Xo.x = (1.0f - a.alpha) * YY.x + a.alpha * X2.x;
                     Xo.y = (1.0f - a.alpha) * YY.y + a.alpha * X2.y;
@@ -761,7 +857,7 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
                     Xo.w = (1.0f - a.alpha) * YY.w + a.alpha * X2.w;
                 }
                 float4 M4 = zero4, Q4 = zero4;
-                if (si.acc) {
+                if (si.acc && !ULA) {
                     float4 bm = zero4, bq = zero4;
                     if (need_prev) {
                         // DMA of row q was issued just before the previous row's stores
@@ -797,7 +893,7 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
                 const bool rowcore = q >= qc0 && q < qc1;
                 {
                     const int ns = rowcore ? nst : 0;   // this row's stores (both steps)
-                    c1 = c2 + 2 + ns;
+                    c1 = c2 + nd + ns;
                     c2 = ns;
                 }
                 // GEN: the lanes' columns of this row's segment
@@ -805,7 +901,7 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
                 const bool corer = GEN ? (rc.g.on && gjr < W && gjr >= rc.g.cc0 && gjr < rc.g.cc1) : core;
                 if (rowcore && corer) {
                     const size_t base = rc.g.pbase + (size_t)rc.r * L + gjr;
-                    st_nt(a.x[par_out] + base, Xo);
+                    if (!ULA) st_nt(a.x[par_out] + base, Xo);   // (FRONT_ULA: X' goes out with the held stores)
                     float* u2o = a.u2[par_out] + 2 * base;
                     st_nt(u2o, UA);
                     st_nt(u2o + 4, UB);
@@ -879,7 +975,8 @@ __global__ void __launch_bounds__(TV_THREADS) tv_stream_kernel(const TvArgs a) {
     // the previous step's pending early-stop redo (rare): all workgroups in parallel, then one grid barrier;
     // launch_mask 4 (redo_only): the redo alone.  (Not with FRONT_STEP_GIVEN: this launch's Y was computed from the X
     // the redo would only now correct -- psgla_tv_step never sets par_redo there, the finaliser recomputes serially.)
-    if constexpr (FRONT == FRONT_INPAINT) {
+    // (FRONT_ULA as the inpainting front: its redo reads only ping-pong state and in-kernel noise)
+    if constexpr (FRONT == FRONT_INPAINT || FRONT == FRONT_ULA) {
         if (a.par_redo && (a.fin_inline || a.redo_only)) {
             const int pend = __builtin_amdgcn_readfirstlane(a.redo[0]);
             if (pend & 1) {
@@ -1010,9 +1107,15 @@ static StreamInstance stream_instance(bool exact, bool alpha1, bool gen, bool ha
     const int slot = (exact ? 8 : 0) | (alpha1 ? 4 : 0) | (gen ? 2 : 0) | (half ? 1 : 0);
 #define PSGLA_STREAM(E, A, G, HF) \
     if (exact == E && alpha1 == A && gen == G && half == HF) return {&tv_stream_kernel<E, A, G, HF, PSGLA_STREAM_FRONT>, slot};
-    PSGLA_STREAM(true, true, false, false) PSGLA_STREAM(true, true, true, false) PSGLA_STREAM(true, false, false, false) PSGLA_STREAM(true, false, true, false)
-    PSGLA_STREAM(false, true, false, false) PSGLA_STREAM(false, true, true, false) PSGLA_STREAM(false, false, false, false) PSGLA_STREAM(false, false, true, false)
-    PSGLA_STREAM(true, true, true, true) PSGLA_STREAM(true, false, true, true) PSGLA_STREAM(false, true, true, true) PSGLA_STREAM(false, false, true, true)
+    // (PSGLA_STREAM_NO_ALPHA1: tv_stream_ula.hip -- the ULA step has the x2-separate layout only)
+#ifndef PSGLA_STREAM_NO_ALPHA1
+    PSGLA_STREAM(true, true, false, false) PSGLA_STREAM(true, true, true, false)
+    PSGLA_STREAM(false, true, false, false) PSGLA_STREAM(false, true, true, false)
+    PSGLA_STREAM(true, true, true, true) PSGLA_STREAM(false, true, true, true)
+#endif
+    PSGLA_STREAM(true, false, false, false) PSGLA_STREAM(true, false, true, false)
+    PSGLA_STREAM(false, false, false, false) PSGLA_STREAM(false, false, true, false)
+    PSGLA_STREAM(true, false, true, true) PSGLA_STREAM(false, false, true, true)
 #undef PSGLA_STREAM
     return {nullptr, 0};
 }

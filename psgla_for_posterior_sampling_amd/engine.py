@@ -37,6 +37,26 @@ class BlurTerm(NamedTuple):
 
 
 class FusedTvChains:
+    # What a subclass with another fused step changes (FusedUlaTvChains): the entry points, the descriptor
+    # (_new_desc), and whether the TV primal x2 always has buffers of its own (else only when alpha != 1)
+    _STEP_FN, _KERNEL_FN = "psgla_tv_step", "psgla_tv_step_kernel"
+    X2_OWN = False
+
+    def _new_desc(self):
+        """(descriptor passed to the entry point, its PsglaTvStep part)."""
+        d = N.PsglaTvStep()
+        return d, d
+
+    @staticmethod
+    def _band_only(kernel_variant: str, H: int, tv) -> bool:
+        """The shape can only run on the band kernel, which needs unpadded rows (ldw == W)."""
+        return kernel_variant == "band"
+
+    @staticmethod
+    def _tv(desc):
+        """The PsglaTvStep part of a descriptor of this engine."""
+        return desc.tv if isinstance(desc, N.PsglaUlaTvStep) else desc
+
     def __init__(self, init: torch.Tensor, y: torch.Tensor, mask_u8: torch.Tensor | None, *, c1: float, c2: float,
                  sigma2: float, alpha: float, ths: float, tv: K.TvConstants, seed: int, n_iter: int,
                  n_inter: int, n_inter_mmse: int, chain0: int = 0, exact: bool = False,
@@ -57,11 +77,11 @@ class FusedTvChains:
         # of the first W columns
         if kernel_variant not in KERNEL_VARIANTS:
             raise ValueError(f"kernel_variant must be one of {sorted(KERNEL_VARIANTS)}")
-        self.ldw = Wd if (Wd % 4 == 0 or kernel_variant == "band") else (Wd + 3) // 4 * 4
+        self.ldw = Wd if (Wd % 4 == 0 or self._band_only(kernel_variant, H, tv)) else (Wd + 3) // 4 * 4
         self.pshape = (B, C, H, self.ldw)
         self.device = dev
         self.alpha = float(alpha)
-        self.alpha1 = self.alpha == 1.0
+        self.alpha1 = self.alpha == 1.0 and not self.X2_OWN      # x2 is X: no buffers of its own
         f32 = dict(dtype=torch.float32, device=dev)
         self.x = [self._padded(init), torch.zeros(self.pshape, **f32)]
         self.u2 = [torch.zeros(self.pshape + (2,), **f32), torch.zeros(self.pshape + (2,), **f32)]
@@ -94,7 +114,7 @@ class FusedTvChains:
         self.n_iter = int(n_iter)
         self.warm_first = warm and self.alpha1
 
-        d = N.PsglaTvStep()
+        desc, d = self._new_desc()
         d.B, d.C, d.H, d.W = B, C, H, Wd
         d.ldw = self.ldw
         for i in range(2):
@@ -135,7 +155,7 @@ class FusedTvChains:
         # (not with the deblurring data term: the next launch's Y is computed before a redo could correct X, so
         # the step's finaliser recomputes stopped chains itself and settle() has nothing to do)
         d.redo = self.work.redo.data_ptr() if (parallel_redo and blur is None) else None
-        self.desc = d
+        self.desc = desc
         self._unsettled = False
         self.sched_struct = self.sched.struct(True, 0)
         if self.warm_first:
@@ -169,8 +189,8 @@ class FusedTvChains:
             K.blur_langevin_pitched(self.x[0], self.x[1], self.y, bl.taps_conv, bl.taps_corr, bl.l, bl.sigma2,
                                     self.c1, self.c2, self.seed, self.chain0, 0, self.Ybuf, self.W, exact=bl.exact,
                                     d_step=self.sched.d_step)
-        N.check(N.lib().psgla_tv_step(ctypes.byref(desc), ctypes.byref(self.sched_struct), K._stream()),
-                "psgla_tv_step")
+        N.check(getattr(N.lib(), self._STEP_FN)(ctypes.byref(desc), ctypes.byref(self.sched_struct), K._stream()),
+                self._STEP_FN)
 
     def step(self, n: int = 1):
         """Launch n steps eagerly (async on the current stream)."""
@@ -193,9 +213,9 @@ class FusedTvChains:
         """Apply a pending early-stop redo of the last step (launch_mask 4: the stopped chains' part of that
         step, recomputed in parallel; nothing when no chain stopped).  Every result accessor calls it."""
         desc = self.desc if desc is None else desc
-        if self._unsettled and desc.redo:
-            d = N.PsglaTvStep.from_buffer_copy(desc)
-            d.launch_mask = 4
+        if self._unsettled and self._tv(desc).redo:
+            d = type(desc).from_buffer_copy(desc)
+            self._tv(d).launch_mask = 4
             self._launch(d)
         self._unsettled = False
 
@@ -273,7 +293,7 @@ class FusedTvChains:
         psgla_tv_step_kernel: the small-batch tile kernel when its tiles fit on the CUs at once, else
         the row stream (W % 4 == 0 rows -- always, the engine pads rows --, 1 <= n_tv <= 10, H >= 2); the band
         kernel otherwise or when forced)."""
-        k = N.lib().psgla_tv_step_kernel(ctypes.byref(self.desc))
+        k = getattr(N.lib(), self._KERNEL_FN)(ctypes.byref(self.desc))
         if k < 0:
             raise RuntimeError(N.lib().psgla_last_error().decode())
         return {0: "tv_main_kernel", 1: "tv_stream_kernel", 3: "tv_tile_kernel"}[k]
@@ -284,8 +304,8 @@ class FusedTvChains:
         Used to time the dominant kernel alone.  A pending early-stop redo of the last step is settled first:
         this launch rewrites the ping-pong buffer that redo reads its inputs from."""
         self.settle()
-        d = N.PsglaTvStep.from_buffer_copy(self.desc)
-        d.launch_mask = 1
+        d = type(self.desc).from_buffer_copy(self.desc)
+        self._tv(d).launch_mask = 1
         for i in range(n):
             self._launch(d, stencil=i == 0)     # (deblurring: the step's Y once, then the TV kernel alone)
 
@@ -371,6 +391,38 @@ class FusedTvChains:
         M = [torch.squeeze(b1[k]) for k in range(nb)] if b1 is not None else []
         M2 = [torch.squeeze(b2[k]) for k in range(nb)] if b2 is not None else []
         return Xlist, M, M2
+
+
+class FusedUlaTvChains(FusedTvChains):
+    """B independent PnP-ULA chains whose prior is the warm-started TV prox (a DenoiserPrior over a TVDenoiser) with
+    the inpainting fidelity, one fused launch per step (psgla_tv_ula_step: restoration_algorithms.py:103-144 with
+    sampling_images.py:156-157 and :295).  Everything but the step's entry point and descriptor is FusedTvChains:
+    padded pitch, ping-pong buffers, workspace, eager step / capture / replay / settle / check_handoff, results.
+    The prox output is never the chain state, so the TV primal always has buffers of its own (no warm_first case);
+    deepinv's early stop is per chain: every chain is one reference run.  No tile kernel yet: kernel_variant is
+    "auto", "band" or "stream"."""
+
+    _STEP_FN, _KERNEL_FN = "psgla_tv_ula_step", "psgla_tv_ula_step_kernel"
+    X2_OWN = True
+
+    def __init__(self, init: torch.Tensor, y: torch.Tensor, mask_u8: torch.Tensor, *, delta: float, lambd: float,
+                 brw: float, c_min: float, c_max: float, s2: float, sigma2: float, alpha: float, ths: float,
+                 tv: K.TvConstants, seed: int, n_iter: int, n_inter: int, n_inter_mmse: int, **kw):
+        if kw.get("blur") is not None:
+            raise ValueError("the fused ULA + TV step has the inpainting data term only")
+        self._ula = (float(delta), float(lambd), float(brw), float(c_min), float(c_max), float(s2))
+        super().__init__(init, y, mask_u8, c1=0.0, c2=0.0, sigma2=sigma2, alpha=alpha, ths=ths, tv=tv, seed=seed,
+                         n_iter=n_iter, n_inter=n_inter, n_inter_mmse=n_inter_mmse, **kw)
+
+    @staticmethod
+    def _band_only(kernel_variant: str, H: int, tv) -> bool:
+        # no tile kernel: what the row stream does not take (n_tv > 10, H < 2) runs on the band kernel, unpadded
+        return kernel_variant == "band" or tv.n_it > 10 or H < 2
+
+    def _new_desc(self):
+        u = N.PsglaUlaTvStep()
+        u.delta, u.lambd, u.brw, u.c_min, u.c_max, u.s2 = self._ula
+        return u, u.tv
 
 
 def _capture(body, k: int, device):
