@@ -162,7 +162,8 @@ typedef struct PsglaTvStep {
     int32_t* redo;            /* (ABI 11) device int[4 + B], zero-initialised, or NULL: the parallel early-stop
                                  redo (above): [0] pending (bit 0) and the stopped step's TV restart flag
                                  (bit 1), [1] the grid-barrier count, [4 + g] chain g's inner iterations  */
-    int32_t data_term;        /* (ABI 12) 0: inpainting data term in the kernel; 1: y is this step's Y (above) */
+    int32_t data_term;        /* (ABI 12) 0: inpainting data term in the kernel; 1: y is this step's Y (above);
+                                 2 (psgla_tv_ula_step only): y is this step's data gradient (below)   */
 } PsglaTvStep;
 
 int psgla_tv_step(const PsglaTvStep* d, const PsglaSchedule* s, void* stream);
@@ -173,7 +174,8 @@ int psgla_tv_step_kernel(const PsglaTvStep* d);
 
 /* ---------------------------------------------------------------------------------
  * psgla_tv_ula_step: ONE fused PnP-ULA Langevin step whose denoiser is the warm-started TV prox ("MYULA with a TV
- * prior") and whose data term is the inpainting fidelity, for B chains.  Replaces one iteration of
+ * prior") and whose data term is the inpainting fidelity (tv.data_term 0) or is given (tv.data_term 2: deblurring),
+ * for B chains.  Replaces one iteration of
  *   restoration_algorithms.py:103-144 with
  *   prior_grad = sampling_images.py:156-157  (alpha*(D(x, s1) - x)/s2, D = deepinv 0.2.1 TVDenoiser(n_it_max))
  *   data_grad  = sampling_images.py:295      (-mask*(x - y)/sigma2)
@@ -185,8 +187,16 @@ int psgla_tv_step_kernel(const PsglaTvStep* d);
  *   tv.alpha       the prior's alpha (a coefficient, not a relaxation);
  *   tv.ths         s1;
  *   tv.c1, tv.c2   unused;
- *   tv.data_term   must be 0 (the inpainting data term is computed in the kernel from y, mask and sigma2); any
- *                  other value is rejected;
+ *   tv.data_term   0: the inpainting data term is computed in the kernel from y, mask and sigma2;
+ *                  2: "the data gradient is given" -- `y` holds this step's gd(X) (deblurring: -A^T(A X - y)/sigma2,
+ *                  written by an earlier launch on the same stream, psgla_blur_grad_pitched) with row pitch ldw and
+ *                  y_chain_stride == C*H*ldw (0 is accepted only for B == 1); the step reads it where it reads the
+ *                  observation and the mask with data_term 0; `mask` and sigma2 are unused (mask may be NULL);
+ *                  padding columns of gd are never read into the image.  `redo` must be NULL (rejected otherwise:
+ *                  the next launch's gd is computed from an X a redo would only then correct -- psgla_tv_step's
+ *                  data_term 1 argument), launch_mask 4 is a no-op, and the finaliser's serial recompute re-reads
+ *                  gd from the same buffer.  The kernel choice is data_term 0's.
+ *                  Any other value (1 included) is rejected;
  *   tv.x2[0], tv.x2[1]  must be non-NULL: the prox output D is never the chain state X', so the TV primal always
  *                  has ping-pong buffers of its own (the kernels' "alpha != 1" layout; there is no other).
  * One call, per chain and step i:
@@ -198,15 +208,16 @@ int psgla_tv_step_kernel(const PsglaTvStep* d);
  *       gp = (alpha*(D - X))/s2;  gd = ((-m)*(X - y))/sigma2;
  *       out = X > c_min ? X : c_min;  proj = out < c_max ? out : c_max;
  *       gpi = (gp - (X - proj)/lambd) + gd;  X' = (X + delta*gpi) + brw*Z
- *     (bit-identical to TVDenoiser.forward + pnpula_prior_update for one chain); fast mode fuses into fma and
- *     multiplies by reciprocals formed on the host;
+ *     (bit-identical to TVDenoiser.forward + pnpula_prior_update for one chain; data_term 2: gd is the given value,
+ *     bit-identical to TVDenoiser.forward + psgla_blur_grad + pnpula_prior_update(gd)); fast mode fuses into fma and
+ *     multiplies by reciprocals formed on the host (data_term 2: t = fma(proj - X, 1/lambd, gd));
  *   - step i writes x[(i+1)&1] = X', x2[(i+1)&1] = D and u2[(i+1)&1], the accumulators and samples of X' by
  *     PsglaSchedule, then clears `fresh` and advances the step;
  *   - deepinv's early stop is decided per chain, exactly as in psgla_tv_step: a stopped chain's step is recomputed
  *     with its shorter iteration count and the same Z.
  * launch_mask, kernel_variant (0, 1, 2), stream_wgs, stream_windows, ldw and norms_copies keep their meaning.  The
- * parallel early-stop redo IS supported (it reads only ping-pong state and in-kernel noise, as the inpainting front's):
- * a non-NULL `redo` and launch_mask 4 work as in psgla_tv_step, on the row stream.
+ * parallel early-stop redo IS supported with data_term 0 (it reads only ping-pong state and in-kernel noise, as the
+ * inpainting front's): a non-NULL `redo` and launch_mask 4 work as in psgla_tv_step, on the row stream.
  * Kernels: the row stream (tv_stream_kernel, 1 <= n_tv <= 10, H >= 2, ldw % 4 == 0) and the band kernel + finaliser
  * (n_tv 11-24, H < 2 or kernel_variant 1; ldw == W).  There are no tile-kernel instances yet: kernel_variant 4 is
  * rejected, and shapes psgla_tv_step would give to tiles run on the stream (or the band kernel when n_tv > 10).
@@ -333,6 +344,15 @@ int psgla_blur_langevin(const float* X_even, const float* X_odd, const float* y,
                         const float* hconv, const float* hcorr, int32_t l, float* Y, int32_t B, int32_t C, int32_t H,
                         int32_t W, int32_t ld, float sigma2, float c1, float c2, uint64_t seed, int32_t chain0,
                         const int64_t* d_step, int64_t step_offset, int32_t exact, void* stream);
+/* (ABI 12, symbol added) The data gradient alone, g = -A^T(A X - y) / sigma2, with psgla_blur_langevin's pitch and
+ * parity rules: psgla_blur_grad(..., g, Y = NULL) on buffers of row pitch ld, the input chosen by the step's parity.
+ * For ld == W (or 0) it is bit-identical to psgla_blur_grad's g; for ld > W the image columns are bit-identical and
+ * the padding columns of g are not touched.  A captured [psgla_blur_grad_pitched, psgla_tv_ula_step(data_term 2)]
+ * pair replays at any step parity. */
+int psgla_blur_grad_pitched(const float* X_even, const float* X_odd, const float* y, int64_t y_chain_stride,
+                            const float* hconv, const float* hcorr, int32_t l, float* g, int32_t B, int32_t C,
+                            int32_t H, int32_t W, int32_t ld, float sigma2, const int64_t* d_step, int64_t step_offset,
+                            int32_t exact, void* stream);
 /* Fast mode (exact = 0) runs rank-1 taps (the reference's h^T h kernels) as separable row / column passes
  * (results within fp32 rounding of the 2-D stencil); enable = 0 keeps every call on the 2-D stencil
  * (process-wide switch, for A/B and tests; default 1). */

@@ -95,6 +95,8 @@ _SIGNATURES = {
                                 c_f, c_f, c_f, c_u64, c_i32, c_vp, c_i64, c_i32, c_vp]),
     "psgla_blur_langevin": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32,
                                     c_i32, c_f, c_f, c_f, c_u64, c_i32, c_vp, c_i64, c_i32, c_vp]),
+    "psgla_blur_grad_pitched": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32,
+                                        c_i32, c_f, c_vp, c_i64, c_i32, c_vp]),
     "psgla_blur_set_separable": (c_i32, [c_i32]),
     "psgla_advance_step": (c_i32, [c_vp, c_vp]),
     "psgla_bias_act": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i32, c_vp]),

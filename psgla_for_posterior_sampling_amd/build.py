@@ -30,8 +30,8 @@ REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 # (the stream / tile kernels' "Y is given" instances are units of their own -- each includes its kernel's source
 # with another front selected -- so they compile beside the inpainting instances instead of after them; so are the
-# stream kernel's PnP-ULA instances, tv_stream_ula)
-UNITS = ["api", "tv_stream", "tv_stream_given", "tv_stream_ula", "tv_tile", "tv_tile_given", "tv_band", "blur", "elementwise"]
+# stream kernel's PnP-ULA instances, tv_stream_ula and -- the data gradient given -- tv_stream_ula_given)
+UNITS = ["api", "tv_stream", "tv_stream_given", "tv_stream_ula", "tv_stream_ula_given", "tv_tile", "tv_tile_given", "tv_band", "blur", "elementwise"]
 SOURCES = [os.path.join(CSRC, u + ".hip") for u in UNITS]
 HEADERS = [os.path.join(CSRC, "noise.hpp"), os.path.join(CSRC, "psgla_common.hpp"),
            os.path.join(REPO, "include", "psgla_hip.h")]
@@ -54,7 +54,7 @@ def up_to_date() -> bool:
     if not os.path.exists(OUT):
         return False
     t = os.path.getmtime(OUT)
-    # (tv_stream_given / tv_stream_ula / tv_tile_given include their kernel's source, which is in SOURCES too)
+    # (tv_stream_given / tv_stream_ula / tv_stream_ula_given / tv_tile_given include their kernel's source, which is in SOURCES too)
     return all(os.path.getmtime(s) <= t for s in SOURCES + HEADERS)
 
 

@@ -137,7 +137,8 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
     if (mask == 0) mask = 3;
     // launch_mask 4: settle a pending early-stop redo of the last step (the kernel redoes the stopped chains' part
     // of it, nothing else), then clear the pending flag; only the stream / tile kernels with a redo buffer have one
-    // (with a given Y -- data_term 1 -- there is no parallel redo: launch_mask 4 is a no-op)
+    // (with a given Y -- data_term 1 -- or a given data gradient -- psgla_tv_ula_step's data_term 2 -- there is no
+    // parallel redo: launch_mask 4 is a no-op)
     if (mask == 4) {
         // (FRONT_ULA: the row stream's redo, as the inpainting front's; it has no tile instances)
         constexpr int FR = FRONT == FRONT_ULA ? FRONT_ULA : FRONT_INPAINT;
@@ -147,7 +148,7 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
         s.redo_only = 1;
         int rc = 0;
         if (a.tile_r > 0) {
-            if constexpr (FRONT != FRONT_ULA) {
+            if constexpr (!front_is_ula(FRONT)) {
                 const int grid = P * s.nbands * s.st_nsegs;
                 const bool gen = !(s.ldw == s.W && s.st_nsegs == 1);
                 s.par_redo = grid_resident(grid, tile_blocks_per_cu<FRONT_INPAINT>(EXACT, ALPHA1, gen, s.tile_r)) ? 1 : 0;
@@ -172,8 +173,8 @@ static int launch_tv(const TvArgs& a, hipStream_t st, int mask = 3) {
     // instances this launch takes (never referenced for the bare prox, which has none)
     constexpr int FS = FRONT == FRONT_GIVEN ? FRONT_INPAINT : FRONT;
     if (mask & 1) {
-        if (FRONT != FRONT_GIVEN && FRONT != FRONT_ULA && a.tile_r > 0) {
-          if constexpr (FRONT != FRONT_ULA) {
+        if (FRONT != FRONT_GIVEN && !front_is_ula(FRONT) && a.tile_r > 0) {
+          if constexpr (!front_is_ula(FRONT)) {
             TvArgs s = a;
             s.fin_inline = (mask & 2) ? 1 : 0;
             const int grid = P * s.nbands * s.st_nsegs;                   // tile_kernel: one workgroup per tile
@@ -334,12 +335,15 @@ static int select_step_kernel(const PsglaTvStep* d, TvArgs& a, bool tiles = true
 
 // psgla_tv_step's checks of a descriptor and its argument block (everything but the kernel selection); shared with
 // psgla_tv_ula_step, whose embedded descriptor has the same geometry, state, observation, TV constants and schedule
-static int tv_step_args(const PsglaTvStep* d, const PsglaSchedule* s, TvArgs& a) {
+// (ula: the caller is psgla_tv_ula_step, whose data_term 2 -- the data gradient given, ula_check -- has data_term 1's
+// buffer rules: y one (C, H, ldw) block per chain, no mask, no parallel redo)
+static int tv_step_args(const PsglaTvStep* d, const PsglaSchedule* s, TvArgs& a, bool ula = false) {
     int rc = check_tv_common(d->B, d->C, d->H, d->W, d->n_tv);
     if (rc) return rc;
     const bool alpha1 = d->x2[0] == nullptr;
-    if (d->data_term != 0 && d->data_term != 1) return fail(0, "psgla_tv_step: data_term must be 0 (inpainting) or 1 (Y given)");
-    const bool given = d->data_term == 1;
+    if (d->data_term != 0 && d->data_term != 1 && !(ula && d->data_term == 2))
+        return fail(0, "psgla_tv_step: data_term must be 0 (inpainting) or 1 (Y given)");
+    const bool given = d->data_term != 0;
     if (!d->x[0] || !d->x[1] || !d->u2[0] || !d->u2[1] || !d->y || (!given && !d->mask) || !d->norms || !d->arrive ||
         !d->fresh)
         return fail(0, "psgla_tv_step: missing buffer");
@@ -372,10 +376,11 @@ static int tv_step_args(const PsglaTvStep* d, const PsglaSchedule* s, TvArgs& a)
         // Y of this step, written by an earlier launch on the stream: one (C, H, ldw) block per chain.  The parallel
         // redo would run inside the next step's launch, after that step's Y was computed from an X not yet
         // corrected: the finaliser's serial recompute (which re-reads Y from the same buffer) is the only one.
-        if (d->redo) return fail(0, "psgla_tv_step: redo must be NULL with data_term 1 (the finaliser recomputes serially)");
+        // (psgla_tv_ula_step's data_term 2: the same argument for the next launch's data gradient.)
+        if (d->redo) return fail(0, "psgla_tv_step: redo must be NULL with a given Y / data gradient (the finaliser recomputes serially)");
         const long long cs = (long long)d->C * d->H * a.ldw;
         if (d->y_chain_stride != cs && !(d->B == 1 && d->y_chain_stride == 0))
-            return fail(0, "psgla_tv_step: data_term 1 needs y_chain_stride == C*H*ldw");
+            return fail(0, "psgla_tv_step: a given Y / data gradient needs y_chain_stride == C*H*ldw");
         a.y_cs = cs;
         a.mask = nullptr; a.m_cs = 0;
     }
@@ -385,8 +390,12 @@ static int tv_step_args(const PsglaTvStep* d, const PsglaSchedule* s, TvArgs& a)
 
 // What psgla_tv_ula_step requires of its embedded descriptor beyond psgla_tv_step's checks (0: fine; else g_err set)
 static int ula_check(const PsglaTvStep* t) {
-    if (t->data_term != 0)
-        return fail(0, "psgla_tv_ula_step: tv.data_term must be 0 (the inpainting data term is computed in the kernel)");
+    if (t->data_term != 0 && t->data_term != 2)
+        return fail(0, "psgla_tv_ula_step: tv.data_term must be 0 (the inpainting data term is computed in the kernel) "
+                       "or 2 (the data gradient is given)");
+    if (t->data_term == 2 && t->redo)
+        return fail(0, "psgla_tv_ula_step: tv.redo must be NULL with data_term 2 (the next launch's data gradient is "
+                       "computed before a redo could correct X; the finaliser recomputes serially)");
     if (!t->x2[0] || !t->x2[1])
         return fail(0, "psgla_tv_ula_step: tv.x2[0] and tv.x2[1] are required (the prox output is never the chain state)");
     if (t->kernel_variant == 4)
@@ -445,7 +454,7 @@ int psgla_tv_ula_step(const PsglaUlaTvStep* d, const PsglaSchedule* s, void* str
     rc = ula_check(t);
     if (rc) return rc;
     TvArgs a;
-    rc = tv_step_args(t, s, a);
+    rc = tv_step_args(t, s, a, true);
     if (rc) return rc;
     if (!(d->lambd != 0.f) || !(d->s2 != 0.f)) return fail(0, "psgla_tv_ula_step: lambd and s2 must be non-zero");
     a.u_delta = d->delta; a.u_lambd = d->lambd; a.u_brw = d->brw; a.u_cmin = d->c_min; a.u_cmax = d->c_max;
@@ -454,7 +463,11 @@ int psgla_tv_ula_step(const PsglaUlaTvStep* d, const PsglaSchedule* s, void* str
     a.u_ca = (float)((double)d->delta * (double)t->alpha / (double)d->s2);
     if (select_step_kernel(t, a, false) < 0) return g_sel_err == g_err ? (int)hipErrorInvalidValue : fail(0, g_sel_err);
     hipStream_t st = (hipStream_t)stream;
-    if (t->exact || !tv_fast_constants(a)) return launch_tv<true, FRONT_ULA, false>(a, st, t->launch_mask);
+    const bool exact = t->exact || !tv_fast_constants(a);
+    if (t->data_term == 2)
+        return exact ? launch_tv<true, FRONT_ULA_GIVEN, false>(a, st, t->launch_mask)
+                     : launch_tv<false, FRONT_ULA_GIVEN, false>(a, st, t->launch_mask);
+    if (exact) return launch_tv<true, FRONT_ULA, false>(a, st, t->launch_mask);
     return launch_tv<false, FRONT_ULA, false>(a, st, t->launch_mask);
 }
 

@@ -19,7 +19,7 @@ namespace psgla {
 // mode).  The taps are kernel arguments (compile-time indices -> SGPR operands).
 // With Y != NULL the Langevin update Y = (X + c1 g) + c2 Z is fused (g is never stored; X is read
 // from the staged tile).
-// Row pitch (psgla_blur_langevin): rows of X, y, g / Y lie BlurArgs::ld >= W elements apart (the fused TV engine's
+// Row pitch (psgla_blur_langevin, psgla_blur_grad_pitched): rows of X, y, g / Y lie BlurArgs::ld >= W elements apart (the fused TV engine's
 // padded pitch); the circular wrap, the tiles and the noise quads are the image's (W), so the image columns do not
 // depend on the pitch, and the padding columns are neither read nor written (W % 4 == 0: 16-byte accesses stay
 // aligned because ld % 4 == 0; otherwise the element path).  X is X[0] at even step indices, X[1] at odd ones
@@ -606,6 +606,21 @@ int psgla_blur_langevin(const float* X_even, const float* X_odd, const float* y,
         return fail(0, "psgla_blur_langevin: ld must be 0, W, or a multiple of 4 >= W");
     return blur_launch(X_even, X_odd, y, y_chain_stride, hconv, hcorr, l, nullptr, Y, B, C, H, W, ld, sigma2, c1, c2,
                        seed, chain0, d_step, step_offset, exact, stream);
+}
+
+// psgla_blur_langevin's pitch and parity rules on the "write g" branch: the data gradient itself, for the fused
+// PnP-ULA + TV step (psgla_tv_ula_step, data_term 2)
+int psgla_blur_grad_pitched(const float* X_even, const float* X_odd, const float* y, int64_t y_chain_stride,
+                            const float* hconv, const float* hcorr, int32_t l, float* g, int32_t B, int32_t C,
+                            int32_t H, int32_t W, int32_t ld, float sigma2, const int64_t* d_step, int64_t step_offset,
+                            int32_t exact, void* stream) {
+    if (!X_even || !X_odd || !y || !hconv || !hcorr || !g || B <= 0 || C <= 0 || H <= 0 || W <= 0)
+        return fail(0, "psgla_blur_grad_pitched: bad arguments");
+    if (ld == 0) ld = W;
+    if (ld < W || (ld != W && ld % 4 != 0))
+        return fail(0, "psgla_blur_grad_pitched: ld must be 0, W, or a multiple of 4 >= W");
+    return blur_launch(X_even, X_odd, y, y_chain_stride, hconv, hcorr, l, g, nullptr, B, C, H, W, ld, sigma2, 0.f, 0.f,
+                       0, 0, d_step, step_offset, exact, stream);
 }
 
 }  // extern "C"

@@ -94,8 +94,11 @@ constexpr float TV_RHO = 0x1.fd70a4p+0f;       // fp32(1.99)
 // (psgla_tv_prox: no ping-pong, no schedule); FRONT_STEP_GIVEN: the fused step whose Y an earlier launch produced
 // (PsglaTvStep.data_term 1: FRONT_INPAINT's whole epilogue, only the front differs -- Y is loaded through yobs);
 // FRONT_ULA: the fused PnP-ULA + TV step (psgla_tv_ula_step): the TV input is X itself, the epilogue applies the ULA
-// update (ula_update, below) where PSGLA applies the relaxation; always the x2-separate layout (ALPHA1 = false)
-enum Front { FRONT_INPAINT = 0, FRONT_GIVEN = 1, FRONT_STEP_GIVEN = 2, FRONT_ULA = 3 };
+// update (ula_update, below) where PSGLA applies the relaxation; always the x2-separate layout (ALPHA1 = false);
+// FRONT_ULA_GIVEN: FRONT_ULA whose data gradient an earlier launch produced (PsglaTvStep.data_term 2 of
+// psgla_tv_ula_step: gd is loaded through yobs where FRONT_ULA loads the observation and the mask -- deblurring)
+enum Front { FRONT_INPAINT = 0, FRONT_GIVEN = 1, FRONT_STEP_GIVEN = 2, FRONT_ULA = 3, FRONT_ULA_GIVEN = 4 };
+constexpr bool front_is_ula(int front) { return front == FRONT_ULA || front == FRONT_ULA_GIVEN; }
 
 struct TvArgs {
     int B, C, H, W;
@@ -106,7 +109,8 @@ struct TvArgs {
     float* mean[2];
     float* sq[2];
     const float* yin;               // FRONT_GIVEN input
-    const float* yobs;              // observation (FRONT_STEP_GIVEN: this step's Y, row pitch ldw)
+    const float* yobs;              // observation (FRONT_STEP_GIVEN: this step's Y, FRONT_ULA_GIVEN: this step's data
+                                    // gradient; both with row pitch ldw)
     long long y_cs;
     const uint8_t* mask;
     long long m_cs;
@@ -171,6 +175,22 @@ __device__ __forceinline__ float ula_update(const TvArgs& a, float X, float D, f
         return (X + a.u_delta * gpi) + a.u_brw * Z;
     }
     const float gd = (mk * (yo - X)) * a.inv_sigma2;
+    const float t = __builtin_fmaf(proj - X, a.u_inv_lambd, gd);
+    const float P = __builtin_fmaf(a.u_brw, Z, __builtin_fmaf(a.u_delta, t, X));
+    return __builtin_fmaf(a.u_ca, D - X, P);
+}
+// The same update with the data gradient given (FRONT_ULA_GIVEN; the deblurring term of sampling_images.py:329-338,
+// written by psgla_blur_grad_pitched).  EXACT: pnpula_prior_update_kernel's operations with a given gd, in its order
+// -- bit-identical to prox + psgla_blur_grad + that kernel; fast: t = fma(proj - X, 1/lambd, gd), the rest as above.
+template <bool EXACT>
+__device__ __forceinline__ float ula_update_given(const TvArgs& a, float X, float D, float gd, float Z) {
+    const float out = (X > a.u_cmin) ? X : a.u_cmin;
+    const float proj = (out < a.u_cmax) ? out : a.u_cmax;
+    if (EXACT) {
+        const float gp = (a.alpha * (D - X)) / a.u_s2;
+        const float gpi = (gp - (X - proj) / a.u_lambd) + gd;
+        return (X + a.u_delta * gpi) + a.u_brw * Z;
+    }
     const float t = __builtin_fmaf(proj - X, a.u_inv_lambd, gd);
     const float P = __builtin_fmaf(a.u_brw, Z, __builtin_fmaf(a.u_delta, t, X));
     return __builtin_fmaf(a.u_ca, D - X, P);
@@ -400,7 +420,7 @@ __device__ __forceinline__ StepInfo step_info(const TvArgs& a, long long step, c
 template <bool EXACT, int FRONT, bool ALPHA1> void launch_band_main(const TvArgs& a, dim3 grid, hipStream_t st);
 template <bool EXACT, int FRONT, bool ALPHA1> void launch_band_finalise(const TvArgs& a, dim3 grid, hipStream_t st);
 // (stream / tile: FRONT_INPAINT or FRONT_STEP_GIVEN, each front's instances in a translation unit of its own;
-// FRONT_ULA: stream instances only, tv_stream_ula.hip)
+// FRONT_ULA / FRONT_ULA_GIVEN: stream instances only, tv_stream_ula.hip / tv_stream_ula_given.hip)
 template <int FRONT> void launch_stream(const TvArgs& a, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen, bool half);
 template <int FRONT> bool launch_tile(const TvArgs& a, dim3 grid, hipStream_t st, bool exact, bool alpha1, bool gen);
 // workgroups of the instance launch_stream / launch_tile would run that one CU holds at once (the runtime's occupancy

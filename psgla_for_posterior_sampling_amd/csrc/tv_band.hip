@@ -23,6 +23,7 @@ __device__ __forceinline__ void band_tile(const TvArgs& a, int plane, int tile, 
     float (*red)[TV_NW][2] = sh.red;
     constexpr int R = TV_R;
     constexpr bool STEP = FRONT != FRONT_GIVEN;       // a Langevin step (FRONT_INPAINT, FRONT_STEP_GIVEN), not the bare prox
+    constexpr bool ULA = front_is_ula(FRONT);         // FRONT_ULA or FRONT_ULA_GIVEN: they differ where the core is stored
     const int lane = threadIdx.x & (WAVE - 1);
     const int w = threadIdx.x >> 6;
     const int H = a.H, W = a.W, C = a.C;
@@ -113,10 +114,10 @@ __device__ __forceinline__ void band_tile(const TvArgs& a, int plane, int tile, 
                         for (int k = 0; k < CPL; ++k) xs[k] = colok[k] ? x2in[base + k] : 0.f;
                     }
                 }
-            } else if (FRONT == FRONT_STEP_GIVEN || FRONT == FRONT_ULA) {
+            } else if (FRONT == FRONT_STEP_GIVEN || ULA) {
                 // the step's Y is given (FRONT_GIVEN's load); x2 start as FRONT_INPAINT.  FRONT_ULA: the prox input is
                 // X itself (no noise, no data term here: the update is applied where the core is stored)
-                const float* yb = FRONT == FRONT_ULA ? a.x[par_in] + base
+                const float* yb = ULA ? a.x[par_in] + base
                                                      : a.yobs + (size_t)b * a.y_cs + (size_t)c * HW + (size_t)gi[r] * W + gj0;
                 const float* xsin = (fresh || ALPHA1) ? a.x[par_in] : a.x2[par_in];
                 if (vec) {
@@ -307,9 +308,28 @@ __device__ __forceinline__ void band_tile(const TvArgs& a, int plane, int tile, 
 #pragma unroll
             for (int k = 0; k < CPL; ++k) Xo[k] = ula_update<EXACT>(a, f4get(yrow, k), x2[r][k], yo[k], mk[k], Z[k]);
         }
+        if (FRONT == FRONT_ULA_GIVEN) {
+            // the same with this step's data gradient given: its row where FRONT_ULA reads the observation and the mask
+            // (one (C, H, W) block per chain, written by an earlier launch; the finaliser's recompute re-reads it)
+            float gd[CPL] = {0.f, 0.f, 0.f, 0.f}, Z[CPL];
+            normal_quad(a.seed, (uint32_t)(a.chain0 + b), (uint32_t)step, TAG_LANGEVIN,
+                        noise_quad((size_t)c * H + gi[r], gj0, W), Z);
+            if (gj0 < W) {
+                const float* gb = a.yobs + (size_t)b * a.y_cs + (size_t)c * HW + (size_t)gi[r] * W + gj0;
+                if (vec) {
+                    const float4 gg = ld4(gb);
+                    gd[0] = gg.x; gd[1] = gg.y; gd[2] = gg.z; gd[3] = gg.w;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < CPL; ++k) gd[k] = colok[k] ? gb[k] : 0.f;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) Xo[k] = ula_update_given<EXACT>(a, f4get(yrow, k), x2[r][k], gd[k], Z[k]);
+        }
 #pragma unroll
         for (int k = 0; k < CPL; ++k) {
-            if (FRONT == FRONT_ULA) break;
+            if (ULA) break;
             // X = (1 - alpha) Y + alpha D(Y)  (restoration_algorithms.py:238); alpha == 1 gives D(Y) exactly
             if (STEP && !ALPHA1)
                 Xo[k] = (1.0f - a.alpha) * f4get(yrow, k) + a.alpha * x2[r][k];
@@ -447,6 +467,7 @@ PSGLA_BAND(false, FRONT_INPAINT, true) PSGLA_BAND(false, FRONT_INPAINT, false) P
 PSGLA_BAND(true, FRONT_STEP_GIVEN, true) PSGLA_BAND(true, FRONT_STEP_GIVEN, false)
 PSGLA_BAND(false, FRONT_STEP_GIVEN, true) PSGLA_BAND(false, FRONT_STEP_GIVEN, false)
 PSGLA_BAND(true, FRONT_ULA, false) PSGLA_BAND(false, FRONT_ULA, false)
+PSGLA_BAND(true, FRONT_ULA_GIVEN, false) PSGLA_BAND(false, FRONT_ULA_GIVEN, false)
 #undef PSGLA_BAND
 
 }  // namespace psgla

@@ -3,8 +3,8 @@
 #include "psgla_common.hpp"
 
 // The front this translation unit instantiates the kernel for: FRONT_INPAINT here, FRONT_STEP_GIVEN through
-// tv_stream_given.hip and FRONT_ULA through tv_stream_ula.hip (which define the macro and include this file), so the
-// instance sets build in parallel.
+// tv_stream_given.hip, FRONT_ULA through tv_stream_ula.hip and FRONT_ULA_GIVEN through tv_stream_ula_given.hip (which
+// define the macro and include this file), so the instance sets build in parallel.
 #ifndef PSGLA_STREAM_FRONT
 #define PSGLA_STREAM_FRONT FRONT_INPAINT
 #endif
@@ -520,7 +520,8 @@ __device__ __forceinline__ void stage_loop(const TvArgs& a, StreamSharedT<A1>& s
 template <bool EXACT, bool ALPHA1, bool GEN, bool HALF, int FRONT>
 __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA1>& sh, const RowMap& rm, const int n,
                                             const bool track, const long long step, const bool fresh) {
-    constexpr bool ULA = FRONT == FRONT_ULA;
+    constexpr bool ULA = front_is_ula(FRONT);              // FRONT_ULA or FRONT_ULA_GIVEN: they differ in the back only
+    constexpr bool UGIVEN = FRONT == FRONT_ULA_GIVEN;      // the data gradient is given (a row of it where y is staged)
     static_assert(!ULA || !ALPHA1, "the ULA step keeps the TV primal in buffers of its own");
     const int lane = threadIdx.x & (WAVE - 1);
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform (scalar branches)
@@ -743,7 +744,8 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
         cursor_init<GEN, HALF>(a, rm, rc_cur, min(bw, Q - 1));
         cursor_init<GEN, HALF>(a, rm, rc_dma, min(bw, Q - 1));
         // FRONT_ULA: the row's observation and mask too (the update is applied here), row and column clamped into
-        // the plane as the front's
+        // the plane as the front's.  FRONT_ULA_GIVEN: the row of this step's data gradient into the observation's slot,
+        // no mask DMA.
         auto back_issue = [&](int q, const RowCursor& rc) {
             if (need_prev || ULA) {
                 const int rr = min(rc.r, H - 1);
@@ -753,7 +755,7 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
                 if (ULA) {
                     const size_t roff = (size_t)rr * L + gjr;
                     glds16(a.yobs + rc.g.ybase + roff, sh.ulaY(bw, bi));
-                    glds4(a.mask + rc.g.mbase + roff, &sh.fmk[bw][bi][0]);
+                    if (!UGIVEN) glds4(a.mask + rc.g.mbase + roff, &sh.fmk[bw][bi][0]);
                 }
                 if (need_prev) {
                     glds16(mean_in + base, &sh.bst[bw][bi][0][0]);
@@ -761,8 +763,14 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
                 }
             }
         };
-        // DMAs of one back_issue (the waits below count them; without FRONT_ULA they wait only when need_prev)
-        const int nd = ULA ? (need_prev ? 4 : 2) : 2;
+        // DMAs of one back_issue (the waits below count them; without FRONT_ULA they wait only when need_prev).
+        // FRONT_ULA: y and the mask (2), + mean / sq (4).  FRONT_ULA_GIVEN: the gradient row alone (1), + mean / sq (3).
+        // The counts that follow from nd: a back wave's vector-memory operations retire in issue order, and between
+        // the DMA of its row q (issued in row q - 4's step, just before that row's stores) and row q's read it issues
+        // the ns(q - 4) stores of row q - 4, the nd DMAs of row q + 2 and the ns(q - 2) stores of row q - 2: row q
+        // waits for vmcnt <= c1 = ns(q - 4) + nd + ns(q - 2) (c2 carries ns(q - 4) over; the first two rows, issued
+        // back to back before the loop, wait for nd and then nd + ns).  At most 3 + 2 * 7 = 17 <= 23 (wait_vm_n).
+        const int nd = ULA ? (UGIVEN ? (need_prev ? 3 : 1) : (need_prev ? 4 : 2)) : 2;
         // vector-memory stores per core row (all lanes of a wave store together; lane 0 is core)
         const int nst = 3 + (ALPHA1 ? 0 : 1) + ((si.acc && (si.blockend || si.liveout)) ? 2 : 0) + (si.sample ? 1 : 0);
         // a row's stores are spread over the wave's two steps: state + accumulators, then the rest
@@ -776,10 +784,17 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
         auto flush_held = [&]() {
             if (!(GEN ? hcore : core)) return;
             if constexpr (ULA) {
-                hX.x = ula_update<EXACT>(a, uX.x, uD.x, uY.x, (float)(uMk & 0xFFu), uZ.x);
-                hX.y = ula_update<EXACT>(a, uX.y, uD.y, uY.y, (float)((uMk >> 8) & 0xFFu), uZ.y);
-                hX.z = ula_update<EXACT>(a, uX.z, uD.z, uY.z, (float)((uMk >> 16) & 0xFFu), uZ.z);
-                hX.w = ula_update<EXACT>(a, uX.w, uD.w, uY.w, (float)(uMk >> 24), uZ.w);
+                if constexpr (UGIVEN) {                 // uY holds the row of the data gradient
+                    hX.x = ula_update_given<EXACT>(a, uX.x, uD.x, uY.x, uZ.x);
+                    hX.y = ula_update_given<EXACT>(a, uX.y, uD.y, uY.y, uZ.y);
+                    hX.z = ula_update_given<EXACT>(a, uX.z, uD.z, uY.z, uZ.z);
+                    hX.w = ula_update_given<EXACT>(a, uX.w, uD.w, uY.w, uZ.w);
+                } else {
+                    hX.x = ula_update<EXACT>(a, uX.x, uD.x, uY.x, (float)(uMk & 0xFFu), uZ.x);
+                    hX.y = ula_update<EXACT>(a, uX.y, uD.y, uY.y, (float)((uMk >> 8) & 0xFFu), uZ.y);
+                    hX.z = ula_update<EXACT>(a, uX.z, uD.z, uY.z, (float)((uMk >> 16) & 0xFFu), uZ.z);
+                    hX.w = ula_update<EXACT>(a, uX.w, uD.w, uY.w, (float)(uMk >> 24), uZ.w);
+                }
                 st_nt(a.x[par_out] + h_base, hX);
                 if (si.acc) {
                     // the block accumulators of X' (the operations of the other fronts' first step)
@@ -844,7 +859,7 @@ __device__ __forceinline__ void stream_pass(const TvArgs& a, StreamSharedT<ALPHA
                     uX = sh.y[q & (SP_YRING - 1)][lane];
                     uZ = sh.ulaZ(q)[lane];
                     uY = sh.ulaY(bw, bi)[lane];
-                    uMk = sh.fmk[bw][bi][lane];
+                    if (!UGIVEN) uMk = sh.fmk[bw][bi][lane];
                     if (need_prev) {
                         uM = sh.bst[bw][bi][0][lane];
                         uQ = sh.bst[bw][bi][1][lane];
@@ -975,7 +990,8 @@ __global__ void __launch_bounds__(TV_THREADS) tv_stream_kernel(const TvArgs a) {
     // the previous step's pending early-stop redo (rare): all workgroups in parallel, then one grid barrier;
     // launch_mask 4 (redo_only): the redo alone.  (Not with FRONT_STEP_GIVEN: this launch's Y was computed from the X
     // the redo would only now correct -- psgla_tv_step never sets par_redo there, the finaliser recomputes serially.)
-    // (FRONT_ULA as the inpainting front: its redo reads only ping-pong state and in-kernel noise)
+    // (FRONT_ULA as the inpainting front: its redo reads only ping-pong state and in-kernel noise; FRONT_ULA_GIVEN as
+    // FRONT_STEP_GIVEN: this launch's gradient was computed from the X a redo would only now correct)
     if constexpr (FRONT == FRONT_INPAINT || FRONT == FRONT_ULA) {
         if (a.par_redo && (a.fin_inline || a.redo_only)) {
             const int pend = __builtin_amdgcn_readfirstlane(a.redo[0]);

@@ -425,6 +425,46 @@ class FusedUlaTvChains(FusedTvChains):
         return u, u.tv
 
 
+class FusedUlaTvDeblurChains(FusedUlaTvChains):
+    """FusedUlaTvChains with the deblurring data term (sampling_images.py:329-338): per step the stencil kernel writes
+    the data gradient gd(X) = -A^T(A X - y) / sigma2 of the step's input into one (B, C, H, ldw) buffer
+    (psgla_blur_grad_pitched: the input picked on the device by the step's parity) and the fused step reads it where
+    the inpainting engine reads the observation and the mask (PsglaTvStep.data_term 2).  Two launches per step; a
+    captured graph of [stencil, step] pairs replays at either parity.  There is no parallel early-stop redo (the next
+    step's gradient is computed before a redo could correct X): the step's finaliser recomputes stopped chains itself,
+    re-reading the gradient, and settle() has nothing to do.  Everything else is inherited."""
+
+    def __init__(self, init: torch.Tensor, y: torch.Tensor, blur: BlurTerm, *, delta: float, lambd: float, brw: float,
+                 c_min: float, c_max: float, s2: float, alpha: float, ths: float, tv: K.TvConstants, seed: int,
+                 n_iter: int, n_inter: int, n_inter_mmse: int, **kw):
+        if not isinstance(blur, BlurTerm):
+            raise TypeError("FusedUlaTvDeblurChains needs a BlurTerm")
+        kw.pop("parallel_redo", None)
+        self._ula = (float(delta), float(lambd), float(brw), float(c_min), float(c_max), float(s2))
+        # FusedTvChains' "blur" set-up is the one this engine needs: no mask, no redo, y_chain_stride = C*H*ldw and a
+        # zero-initialised per-chain buffer that an earlier launch fills -- here with the gradient, not with Y
+        FusedTvChains.__init__(self, init, y, None, c1=0.0, c2=0.0, sigma2=blur.sigma2, alpha=alpha, ths=ths, tv=tv,
+                               seed=seed, n_iter=n_iter, n_inter=n_inter, n_inter_mmse=n_inter_mmse, blur=blur, **kw)
+        self._tv(self.desc).data_term = 2
+
+    @property
+    def G(self) -> torch.Tensor:
+        """The data gradient of the last step run (the buffer the next step's stencil overwrites)."""
+        return self._view(self.Ybuf)
+
+    @property
+    def Y_prev(self):
+        raise AttributeError("Y_prev: PnP-ULA has no Langevin proposal Y; the step's data gradient is G")
+
+    def _launch(self, desc, stencil: bool = True):
+        if stencil:
+            bl = self.blur
+            K.blur_grad_pitched(self.x[0], self.x[1], self.y, bl.taps_conv, bl.taps_corr, bl.l, bl.sigma2, 0,
+                                self.Ybuf, self.W, exact=bl.exact, d_step=self.sched.d_step)
+        N.check(getattr(N.lib(), self._STEP_FN)(ctypes.byref(desc), ctypes.byref(self.sched_struct), K._stream()),
+                self._STEP_FN)
+
+
 def _capture(body, k: int, device):
     """Record `k` calls of `body` into one hipGraph (torch.cuda.CUDAGraph) on a side stream."""
     s = torch.cuda.Stream(device=device)

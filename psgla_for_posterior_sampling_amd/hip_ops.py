@@ -276,6 +276,23 @@ def blur_langevin_pitched(X_even, X_odd, y, hconv, hcorr, l: int, sigma2: float,
     return out
 
 
+def blur_grad_pitched(X_even, X_odd, y, hconv, hcorr, l: int, sigma2: float, step: int, out, W: int,
+                      exact: bool = False, d_step: torch.Tensor | None = None):
+    """psgla_blur_grad_pitched: blur_grad on (B, C, H, ld) buffers whose rows hold W <= ld image columns (the fused
+    TV engine's padded pitch; padding columns of `out` are left as they are); the input is X_even at even step indices
+    (d_step + step), X_odd at odd ones.  For ld == W and one input it is blur_grad, bit for bit."""
+    B, C, H, ld = X_even.shape
+    if tuple(X_odd.shape) != (B, C, H, ld) or tuple(out.shape) != (B, C, H, ld) or tuple(y.shape[1:]) != (C, H, ld):
+        raise ValueError("blur_grad_pitched: X_even, X_odd, y and out must share (C, H, ld)")
+    y_cs = 0 if y.shape[0] == 1 else C * H * ld
+    hc, hr = _host_taps(hconv, l), _host_taps(hcorr, l)
+    N.check(N.lib().psgla_blur_grad_pitched(_ptr(X_even, name="X_even"), _ptr(X_odd, name="X_odd"), _ptr(y, name="y"),
+                                            y_cs, hc.ctypes.data, hr.ctypes.data, int(l), _ptr(out, name="g"), B, C, H,
+                                            int(W), ld, sigma2, d_step.data_ptr() if d_step is not None else None,
+                                            step, int(exact), _stream()), "psgla_blur_grad_pitched")
+    return out
+
+
 def advance_step(d_step: torch.Tensor):
     N.check(N.lib().psgla_advance_step(_ptr(d_step, torch.int64, "d_step"), _stream()), "psgla_advance_step")
 

@@ -26,8 +26,10 @@ Dispatch:
 (``n_it_max`` <= 24) with an :class:`InpaintingFidelity`, which runs :class:`engine.FusedUlaTvChains`: one fused
 launch per step (prox, prior and data gradients, projection, update, accumulators), hipGraph-replayed, deepinv's
 early stop per chain (so every chain of a batch is one reference run; B = 1 is bit-identical to the generic path in
-exact mode).  A TV prior with a :class:`BlurFidelity`, or ``n_it_max`` > 24, stays on ``UlaChains``, whose prox
-decides the early stop on the whole batch tensor.
+exact mode).  The same prior with a :class:`BlurFidelity` runs :class:`engine.FusedUlaTvDeblurChains`: two launches per
+step (the stencil writes the data gradient of the step's input, the same fused step reads it), hipGraph-replayed,
+the early stop per chain as well; the stencil's ``exact`` is ``data_grad.exact``.  A TV prior with ``n_it_max`` > 24
+stays on ``UlaChains``, whose prox decides the early stop on the whole batch tensor.
 The Gaussian noise is the in-kernel "psgla noise v2" stream of (seed, chain) instead of
 torch's generator (whose CUDA stream depends on the device's CU count); extra keyword
 ``chain0`` gives the global id of the first chain when a batch is sharded over GPUs.
@@ -44,7 +46,7 @@ import torch
 
 from . import hip_ops as K
 from .denoisers import DenoiserPrior, DnCNN, DRUNet, TVDenoiser
-from .engine import BlurTerm, DenoiserChains, FusedTvChains, FusedUlaTvChains, UlaChains
+from .engine import BlurTerm, DenoiserChains, FusedTvChains, FusedUlaTvChains, FusedUlaTvDeblurChains, UlaChains
 from .fidelity import BlurFidelity, InpaintingFidelity
 
 DEFAULT_GRAPH_STEPS = int(os.environ.get("PSGLA_GRAPH_STEPS", "50"))
@@ -258,17 +260,24 @@ def pnpula(init, data_grad, prior_grad, delta, lambd, n_iter=5000, n_inter=1000,
         snaps = _Snapshots(path, name, {"n_iter": n_iter, "c_min": c_min, "c_max": c_max, "lambda": lambd,
                                         "delta": delta})
     tv = prior_grad.denoiser if isinstance(prior_grad, DenoiserPrior) else None
-    if (isinstance(tv, TVDenoiser) and tv.n_it_max <= K.N.TV_MAX_FUSED_IT and isinstance(data_grad, InpaintingFidelity)):
-        # MYULA with a TV prior: the prox, both gradients and the update in one launch per step
+    if (isinstance(tv, TVDenoiser) and tv.n_it_max <= K.N.TV_MAX_FUSED_IT
+            and isinstance(data_grad, (InpaintingFidelity, BlurFidelity))):
+        # MYULA with a TV prior: the prox, both gradients and the update in one launch per step (deblurring: the
+        # stencil's launch writes the data gradient first)
         shape4 = tuple(shape) if X.dim() == 4 else (1,) + tuple(shape)
         warm = not tv.needs_restart(shape4)
-        eng = FusedUlaTvChains(X.reshape(shape4), data_grad.y, data_grad.mask_u8, delta=d, lambd=lam, brw=brw,
-                               c_min=float(c_min), c_max=float(c_max),
-                               s2=float(torch.as_tensor(prior_grad.s2).float().item()), sigma2=data_grad.sigma2,
-                               alpha=float(torch.as_tensor(prior_grad.alpha).float().item()),
-                               ths=float(np.float32(float(prior_grad.s1))), tv=tv.constants(), seed=int(seed),
-                               n_iter=n_iter, n_inter=n_inter, n_inter_mmse=n_inter_mmse, chain0=chain0,
-                               exact=tv.exact, tv_x2=tv.x2 if warm else None, tv_u2=tv.u2 if warm else None)
+        common = dict(delta=d, lambd=lam, brw=brw, c_min=float(c_min), c_max=float(c_max),
+                      s2=float(torch.as_tensor(prior_grad.s2).float().item()),
+                      alpha=float(torch.as_tensor(prior_grad.alpha).float().item()),
+                      ths=float(np.float32(float(prior_grad.s1))), tv=tv.constants(), seed=int(seed),
+                      n_iter=n_iter, n_inter=n_inter, n_inter_mmse=n_inter_mmse, chain0=chain0,
+                      exact=tv.exact, tv_x2=tv.x2 if warm else None, tv_u2=tv.u2 if warm else None)
+        if isinstance(data_grad, BlurFidelity):
+            blur = BlurTerm(data_grad.taps_conv, data_grad.taps_corr, data_grad.l, data_grad.sigma2,
+                            bool(data_grad.exact))
+            eng = FusedUlaTvDeblurChains(X.reshape(shape4), data_grad.y, blur, **common)
+        else:
+            eng = FusedUlaTvChains(X.reshape(shape4), data_grad.y, data_grad.mask_u8, sigma2=data_grad.sigma2, **common)
 
         def run_fused(n):
             eng.run(n, graph_steps=graph_steps if n >= 2 * graph_steps else 0)
